@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: denoised 145-frame clips/s at 1000 DDPM steps (BASELINE.json `metric`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--ddpm-steps 1000]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--ddpm-steps 1000] [--dump-outputs DIR]
 
 One "step" = one complete pass of the hot path over one batch: a full PoseNet `eval_losses` run
 (x_T -> x_0 through 1000 ancestral DDPM steps, on-device noise generation included) for `--batch`
@@ -446,11 +446,14 @@ def scheme_bench(args, world, rank, dev, dist):
             bp['mask_vec_vis'] = mask_vec_vis
         return bt, bp
 
+    last = {}
+
     def one_pass():
         gather.drain()
         bt, bp = batches()
         run = run_prox_iterations if ego else run_amass_iterations
-        pose, _, _ = run(sargs, nets, diffs, bt, bp, tds, pds, layer)
+        pose, traj, recs = run(sargs, nets, diffs, bt, bp, tds, pds, layer)
+        last.update(val_output_pose=pose, val_output_traj=traj, **{f'traj_rec_{i}': r for i, r in enumerate(recs)})
         gather.submit(pose)
         return pose
 
@@ -460,6 +463,8 @@ def scheme_bench(args, world, rank, dev, dist):
     assert finite, 'non-finite samples'
     report = rank_report(args, world, rank, dev, dist, gather, pnet)
     if rank == 0:
+        if args.dump_outputs:      # a multi-rank caller receives every rank's clips of the pose output (the all-gather)
+            dumped = dump_outputs(args.dump_outputs, dict(last, val_output_pose=gather.last if dist is not None else out))
         clips = world * B * args.steps
         all_ms = sum(v['total_ms'] for v in prof.values())
         gemm = {k: v for k, v in prof.items() if k.startswith('gemm_') or k.startswith('conv_gemm')}
@@ -483,6 +488,8 @@ def scheme_bench(args, world, rank, dev, dist):
                             'launches_timed': g_n, 'gemm_time_share_of_kernels': g_ms / all_ms if all_ms else None,
                             'kernels': kernels}}
         rec['rank_report'] = report
+        if args.dump_outputs:
+            rec['dump_outputs'] = dumped
         if world == 1 and (not args.no_cpu_baseline or args.config_cpu_baseline):
             try:
                 rec['cpu_baseline'] = cpu_baseline_config(args.workload, B)
@@ -800,6 +807,15 @@ def init_ranks(args):
     return world, rank, dev, dist
 
 
+def barrier(dist):
+    """dist.barrier() -- except on the gloo self-test, whose ranks meet in monitored_barrier(): dist.barrier() looks up the
+    machine's accelerator, and that initialises HIP and opens the GPU in every CPU-only rank."""
+    if dist.get_backend() == 'gloo':
+        dist.monitored_barrier()
+    else:
+        dist.barrier()
+
+
 def timed_region(one_pass, args, world, dev, dist, profile=True, drain=None):
     """W untimed warm-up passes, then EXACTLY K passes bracketed by barrier + device synchronize on both sides; the
     elapsed time is the MAX over ranks.  `drain`: completes what `one_pass` left in flight (the asynchronous result all-gather of
@@ -809,7 +825,7 @@ def timed_region(one_pass, args, world, dev, dist, profile=True, drain=None):
         if drain is not None:
             drain()
         if dist is not None:
-            dist.barrier()
+            barrier(dist)
         if dev.type == 'cuda':
             torch.cuda.synchronize(dev)
     out = None
@@ -907,9 +923,39 @@ class ResultGather:
             self.drains += 1
 
 
+DUMP_CAP_BYTES = 64 << 20       # --dump-outputs: all arrays together
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write what the timed path returned in its last pass as `path/<name>.npy` (float64 stays float64, every other
+    dtype becomes float32).  If the arrays together exceed DUMP_CAP_BYTES, each keeps a fixed, seeded, sorted subset of its
+    leading (clip) axis -- the same subset for arrays of the same length -- so two builds dump the same clips.  Returns the
+    record of what was written (for the JSON line)."""
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in host.values())
+    frac = min(1.0, DUMP_CAP_BYTES / total) if total else 1.0
+    os.makedirs(path, exist_ok=True)
+    rec = {'dir': os.path.abspath(path), 'cap_bytes': DUMP_CAP_BYTES, 'arrays': {}}
+    for name, a in host.items():
+        n = a.shape[0]
+        keep = None
+        if frac < 1.0:
+            k = max(1, int(n * frac))
+            keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+            a = a[keep]
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a))
+        rec['arrays'][name] = {'shape': list(a.shape), 'dtype': str(a.dtype), 'full_leading_dim': n,
+                               'rows_kept': None if keep is None else keep.tolist()}
+    return rec
+
+
 def finish(world, dist):
     if dist is not None:
-        dist.barrier()
+        barrier(dist)
         dist.destroy_process_group()
 
 
@@ -938,13 +984,14 @@ def selftest_bench(args, world, rank, dev, dist):
         # `--workload scheme --gpus 8 --batch 32` shows the record naming BASELINE.json configs[2] before any hardware run does
         stands_for = (scheme_names(args.workload, B, args.ddpm_steps) if args.workload in ('scheme', 'egobody') else
                       (None, f'{args.workload} [see main()]'))
+        dumped = dump_outputs(args.dump_outputs, {'x0': out}) if args.dump_outputs else None
         print(json.dumps({'metric': 'bench launcher self-test (NOT a measurement: stub sampler on CPU/gloo)', 'value': 0.0,
                           'unit': 'none', 'n_gpus': world, 'world_size': world, 'backend': 'gloo', 'steps': args.steps,
                           'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'data': 'selftest-stub',
                           'gathered_clips': int(out.shape[0]), 'ranks_seen': ranks_seen, 'rank_report': report,
                           'config': {'workload': 'selftest', 'stands_for_metric': stands_for[0], 'stands_for_workload': stands_for[1],
                                      'clips_per_gpu': B, 'sharding': sharding_note(args, world, B, dist),
-                                     'cpu_binding': args.cpu_binding}}), flush=True)
+                                     'cpu_binding': args.cpu_binding}, 'dump_outputs': dumped}), flush=True)
     finish(world, dist)
 
 
@@ -981,10 +1028,16 @@ def main(argv=None):
     ap.add_argument('--force-dist', action='store_true',
                     help='initialise the RCCL process group even at world size 1 and run barrier / all-reduce / all-gather '
                          'through it (the multi-GPU plumbing on a 1-GPU box)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed passes, write what the timed path returned in its LAST pass as DIR/<name>.npy (float32 / '
+                         'float64; a fixed, seeded sample of the clips if all of it exceeds 64 MB).  Inputs, weights and noise are seeded: '
+                         'the same arguments give the same inputs in every run, so two builds can be compared output for output')
     argv = sys.argv[1:] if argv is None else list(argv)
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit('bench.py: --gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('bench.py: --steps must be >= 1 and --warmup >= 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # not launched by torch.distributed.run: become the launcher (one rank per GPU)
         if args.backend == 'nccl' and torch.cuda.device_count() < args.gpus:
@@ -1048,6 +1101,8 @@ def main(argv=None):
     report = rank_report(args, world, rank, dev, dist, gather, net)
 
     if rank == 0:
+        if args.dump_outputs:      # a multi-rank caller receives every rank's clips (the all-gather)
+            dumped = dump_outputs(args.dump_outputs, {'x0': gather.last if dist is not None else out})
         clips = world * B * args.steps
         gemm = {k: v for k, v in prof.items() if k.startswith('gemm_')}
         g_ms = sum(v['total_ms'] for v in gemm.values())
@@ -1157,6 +1212,8 @@ def main(argv=None):
             },
         }
         rec['rank_report'] = report
+        if args.dump_outputs:
+            rec['dump_outputs'] = dumped
         if dist is not None:
             rec['process_group'] = {'backend': dist.get_backend(), 'world_size': dist.get_world_size(), 'forced': bool(args.force_dist)}
         if world == 1 and (not args.no_cpu_baseline or args.config_cpu_baseline) and not prox:

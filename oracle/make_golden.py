@@ -648,7 +648,21 @@ def golden_metrics():
     print({k: float(v) for k, v in out.items()})
 
 
+def golden_import_block():
+    """sha256 of the drivers' import block (test_amass_full.py / test_prox_egobody.py lines 10-15, each line stripped): pins
+    tests/test_dropin.py::IMPORT_BLOCK to the drivers' literal text without a checkout."""
+    import hashlib
+    out = {}
+    for name in ('test_amass_full', 'test_prox_egobody'):
+        lines = open(os.path.join(refload.REF_ROOT, name + '.py')).read().split('\n')[9:15]
+        out[name] = np.str_(hashlib.sha256('\n'.join(ln.strip() for ln in lines).encode()).hexdigest())
+    np.savez_compressed(os.path.join(OUT, 'driver_import_block.npz'), first_line=10, last_line=15, **out)
+    print(out)
+
+
 def main():
+    if sys.argv[1:] == ['import_block']:
+        return golden_import_block()
     if sys.argv[1:] == ['metrics']:
         return golden_metrics()
     if sys.argv[1:] == ['eval_losses']:

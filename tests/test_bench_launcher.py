@@ -237,3 +237,97 @@ def test_extras_attach_second_line_and_configs_and_survive_a_failing_child(monke
     calls.clear()
     bench.extras(types.SimpleNamespace(ddpm_steps=1000, batch=64, no_cpu_baseline=True))
     assert not any('--config-cpu-baseline' in c[0] for c in calls)
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_steps_sets_the_number_of_timed_passes():
+    """`--steps K` times exactly K passes after exactly W untimed ones, and ms_per_step is the bracket over K passes / K."""
+    import time
+    import types
+    import torch
+    bench = _bench_module()
+    calls = []
+
+    def one_pass():
+        calls.append(time.perf_counter())
+        time.sleep(0.005)
+        return torch.zeros(1)
+    args = types.SimpleNamespace(steps=7, warmup=2, profile_stride=100)
+    t0 = time.perf_counter()
+    elapsed, out, prof = bench.timed_region(one_pass, args, 1, torch.device('cpu'), None, profile=False)
+    assert len(calls) == 9 and prof == {} and out is not None
+    assert 7 * 0.005 <= elapsed <= time.perf_counter() - t0
+    r = _run(['--gpus', '1', '--backend', 'gloo', '--steps', '0'], {'ROHM_BENCH_SELFTEST': '1'})
+    assert r.returncode != 0 and '--steps must be >= 1' in r.stderr
+
+
+@pytest.mark.parametrize('world', [1, 2])
+def test_dump_outputs_writes_the_last_pass_and_is_reproducible(tmp_path, world):
+    """`--dump-outputs DIR` through the launcher self-test: rank 0 writes what its caller received (all ranks' clips after the
+    all-gather) as DIR/x0.npy in float32, the record names it, and a second run with the same arguments writes the same bytes."""
+    import numpy as np
+    arrays = []
+    for k in range(2):
+        d = tmp_path / f'run{k}'
+        r = _run(['--gpus', str(world), '--backend', 'gloo', '--steps', '3', '--warmup', '1', '--batch', '3', '--dump-outputs', str(d)],
+                 {'ROHM_BENCH_SELFTEST': '1', 'OMP_NUM_THREADS': '1'})
+        assert r.returncode == 0, r.stderr[-2000:]
+        rec = _json_line(r.stdout)
+        assert rec['steps'] == 3 and rec['ms_per_step'] > 0
+        assert sorted(os.listdir(d)) == ['x0.npy'] and rec['dump_outputs']['arrays']['x0']['shape'] == [3 * world, 4]
+        a = np.load(d / 'x0.npy')
+        assert a.dtype == np.float32 and a.shape == (3 * world, 4)
+        assert sorted(set(a[:, 0].tolist())) == list(range(world))
+        arrays.append(a)
+    assert np.array_equal(arrays[0], arrays[1])
+
+
+def test_dump_outputs_caps_the_total_with_a_fixed_sample(tmp_path):
+    """Above 64 MB in all, every array keeps the same seeded, sorted subset of its leading (clip) axis; float64 stays float64,
+    other dtypes become float32; the same arrays give the same files."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    n = 600
+    big = torch.arange(n, dtype=torch.float32)[:, None].repeat(1, 32768)          # 78.6 MB
+    arrays = {'pose': big, 'traj': torch.arange(n, dtype=torch.float64)[:, None].repeat(1, 8), 'mask': torch.ones(n, 3, dtype=torch.int32)}
+    rec = [bench.dump_outputs(str(tmp_path / f'd{k}'), arrays) for k in range(2)]
+    total = sum(os.path.getsize(tmp_path / 'd0' / f'{k}.npy') for k in arrays)
+    assert total <= bench.DUMP_CAP_BYTES
+    pose, traj, mask = (np.load(tmp_path / 'd0' / f'{k}.npy') for k in ('pose', 'traj', 'mask'))
+    assert pose.dtype == np.float32 and traj.dtype == np.float64 and mask.dtype == np.float32
+    kept = rec[0]['arrays']['pose']['rows_kept']
+    assert 1 < len(kept) < n and kept == sorted(kept) and kept == rec[0]['arrays']['traj']['rows_kept']
+    assert pose[:, 0].tolist() == kept and traj[:, 0].tolist() == kept and pose.shape == (len(kept), 32768)
+    assert rec[0]['arrays'] == rec[1]['arrays']
+    assert np.array_equal(pose, np.load(tmp_path / 'd1' / 'pose.npy'))
+    small = bench.dump_outputs(str(tmp_path / 'small'), {'x0': torch.ones(4, 5)})
+    assert small['arrays']['x0']['rows_kept'] is None and np.load(tmp_path / 'small' / 'x0.npy').shape == (4, 5)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_hot_path_are_reproducible(tmp_path):
+    """The real PoseNet path with `--dump-outputs`: x0 of the last timed pass, [B, 294, 1, 143] float32, finite, and bit-identical
+    between two runs with the same arguments (seeded inputs, weights and noise; deterministic kernels)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    out = []
+    for k in range(2):
+        d = tmp_path / f'run{k}'
+        r = subprocess.run([sys.executable, BENCH, '--steps', '2', '--warmup', '1', '--batch', '4', '--ddpm-steps', '10',
+                            '--no-cpu-baseline', '--no-extras', '--dump-outputs', str(d)], env=env, capture_output=True, text=True,
+                           timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+        rec = _json_line(r.stdout)
+        assert rec['steps'] == 2 and rec['dump_outputs']['arrays']['x0']['shape'] == [4, 294, 1, 143]
+        a = np.load(d / 'x0.npy')
+        assert a.dtype == np.float32 and a.shape == (4, 294, 1, 143) and np.isfinite(a).all()
+        out.append(a)
+    assert np.array_equal(out[0], out[1])

@@ -4,7 +4,9 @@
 `eval_losses(...)` call (test_amass_full.py:376-384) lands on the reference's 8-step result.
 
 Every case runs in a child interpreter: the aliases live in `sys.modules`, and this test session also imports the real reference
-under the same names (oracle/refload.py)."""
+under the same names (oracle/refload.py).  The "with a checkout" case runs against a stand-in checkout written into the test's
+temporary directory; tests/golden/driver_import_block.npz pins IMPORT_BLOCK to the drivers' own lines."""
+import hashlib
 import os
 import subprocess
 import sys
@@ -12,8 +14,9 @@ import textwrap
 
 import pytest
 
+from helpers import golden
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference'
 
 # the six statements of the drivers' import block that name the hot path (API surface: module paths and class names)
 IMPORT_BLOCK = """\
@@ -118,9 +121,41 @@ def _run(code, timeout=600):
     return p.stdout
 
 
-def _prelude(with_reference):
-    extra = f'sys.path.insert(0, {REF!r})' if with_reference else ''
+def _prelude(checkout):
+    extra = f'sys.path.insert(0, {checkout!r})' if checkout else ''
     return PRELUDE.format(root=ROOT, extra_path=extra)
+
+
+# the drivers' hot-path modules (rohm_amd.dropin.ALIASES): in the stand-in checkout they fail loudly if the checkout's file is imported
+ALIASED = ('model/posenet.py', 'model/trajnet.py', 'diffusion/gaussian_diffusion_posenet.py', 'diffusion/gaussian_diffusion_trajnet.py',
+           'diffusion/respace.py', 'utils/model_util.py')
+
+
+def _standin_checkout(root):
+    """A RoHM checkout as the drivers see it: namespace packages `model` / `diffusion` / `utils` (no __init__.py), host-code
+    modules that must stay the checkout's (`utils.dist_util`, `utils.fixseed`, `diffusion.logger`), the six aliased modules as
+    decoys, and the two driver scripts with the import block at lines 10-15."""
+    files = {'utils/dist_util.py': 'def dev():\n    return "cpu"\n',
+             'utils/fixseed.py': 'def fixseed(seed):\n    return seed\n',
+             'diffusion/logger.py': 'def log(*args):\n    pass\n'}
+    for rel in ALIASED:
+        files[rel] = f'raise ImportError("the checkout\'s own {rel} was imported: the drop-in alias must win")\n'
+    preamble = ''.join(f'# driver line {i}\n' for i in range(1, 10))
+    for driver in ('test_amass_full.py', 'test_prox_egobody.py'):
+        files[driver] = preamble + IMPORT_BLOCK + 'print("driver body")\n'
+    for rel, text in files.items():
+        path = root / rel
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(text)
+    return str(root)
+
+
+def test_import_block_is_the_drivers_literal_text():
+    """IMPORT_BLOCK equals lines 10-15 of both RoHM drivers (whitespace-stripped), by the digests the fixture took of them."""
+    g = golden('driver_import_block.npz')
+    assert (int(g['first_line']), int(g['last_line'])) == (10, 15)
+    digest = hashlib.sha256('\n'.join(ln.strip() for ln in IMPORT_BLOCK.strip().split('\n')).encode()).hexdigest()
+    assert digest == str(g['test_amass_full']) == str(g['test_prox_egobody'])
 
 
 CHECKS = """\
@@ -135,12 +170,11 @@ assert model.posenet.PoseNet is PoseNet and dropin.installed()
 
 
 @pytest.mark.parametrize('with_reference', [False, True])
-def test_literal_import_block_and_driver_construction(with_reference):
+def test_literal_import_block_and_driver_construction(with_reference, tmp_path):
     """Without a RoHM checkout on sys.path (parents synthesised) and with one (the checkout's `utils` / `diffusion` / `model`
     packages stay the parents: `utils.dist_util`, `utils.fixseed`, `diffusion.logger` keep coming from the checkout)."""
-    if with_reference and not os.path.isdir(os.path.join(REF, 'model')):
-        pytest.skip('no reference checkout in this environment')
-    code = _prelude(with_reference) + IMPORT_BLOCK + CHECKS + SETUP.format(dev='cpu', steps=1000, wseed=3) + CONSTRUCT + textwrap.dedent("""\
+    checkout = _standin_checkout(tmp_path / 'rohm_checkout') if with_reference else None
+    code = _prelude(checkout) + IMPORT_BLOCK + CHECKS + SETUP.format(dev='cpu', steps=1000, wseed=3) + CONSTRUCT + textwrap.dedent("""\
         assert len(model_posenet.state_dict()) >= 108 and diffusion_posenet_eval.num_timesteps == 1000
         assert diffusion_trajnet_eval.num_timesteps == diffusion_trajnet_control_eval.num_timesteps == 100
         assert model_trajnet_control.trajcontrol and not model_trajnet.trajcontrol
@@ -150,13 +184,13 @@ def test_literal_import_block_and_driver_construction(with_reference):
             from utils import dist_util as real_dist_util
             from utils.fixseed import fixseed
             import diffusion.logger
-            assert real_dist_util.__file__.startswith({REF!r}) and fixseed.__module__ == 'utils.fixseed'
-            assert diffusion.logger.__file__.startswith({REF!r})
-            # and the literal lines of the driver file itself
-            lines = open({REF!r} + '/test_amass_full.py').read().split('\\n')[9:15]
+            assert real_dist_util.__file__.startswith({checkout!r}) and fixseed.__module__ == 'utils.fixseed'
+            assert diffusion.logger.__file__.startswith({checkout!r})
+            # and the import block as it stands in the driver files (lines 10-15)
+            lines = open({checkout!r} + '/test_amass_full.py').read().split('\\n')[9:15]
             assert [l.strip() for l in lines] == [l.strip() for l in {IMPORT_BLOCK!r}.strip().split('\\n')], lines
             exec('\\n'.join(lines))
-            lines = open({REF!r} + '/test_prox_egobody.py').read().split('\\n')[9:15]
+            lines = open({checkout!r} + '/test_prox_egobody.py').read().split('\\n')[9:15]
             exec('\\n'.join(lines))
             """)
     code += textwrap.dedent("""\
@@ -188,7 +222,7 @@ def test_runner_executes_a_driver_script_unmodified(tmp_path):
 def test_driver_eval_losses_call_through_the_dropin_vs_reference_golden():
     """The drivers' exact sampling call on the HIP networks, reached through the aliased import block, against the reference's own
     8-step run (tests/golden/posenet_loop8.npz)."""
-    code = _prelude(False) + IMPORT_BLOCK + textwrap.dedent("""\
+    code = _prelude(None) + IMPORT_BLOCK + textwrap.dedent("""\
         from helpers import cpu_noise_sequence, golden, seeded, max_abs
         g = golden('posenet_loop8.npz')
         """) + SETUP.format(dev='cuda:0', steps='int(g["steps"])', wseed='int(g["weight_seed"])') + textwrap.dedent("""\
