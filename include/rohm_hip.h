@@ -347,8 +347,7 @@ int rohm_trajnet_sample_loop(const rohm_trajnet_t* h, float* x, const float* con
  * launch per denoising step, an XCD's workgroups stay with its clips and meet through its L2 between the layers -- csrc/trajnet_resident.hip:
  * the default for TrajNet at B <= 64 on a device that passed the exchange probe, opt-in ROHM_TRAJ_RESIDENT=1 for TrajControl, off with
  * ROHM_TRAJ_RESIDENT=0; when it runs, rohm_trajnet_sample_loop waits for the stream once at its end to read the exchange's error word, and
- * a wait that expired hands the call back to form 0 with x restored), 2 the recorded step (opt-in ROHM_TRAJNET_GRAPH=1).  No counterpart in
- * the reference. */
+ * a wait that expired hands the call back to form 0 with x restored).  No counterpart in the reference. */
 int rohm_trajnet_loop_mode(void);
 
 /* ------------------------------------------------------------------------- SMPL-X + guidance

@@ -41,12 +41,9 @@ def find_hipcc():
     return None
 
 
-def build(force=False, verbose=True, out=None, diag=None):
-    """Build the library; `out` / `diag` build a second copy (scripts/gemm_timeline.py uses a ROHM_GEMM_DIAGNOSTICS build
-    under ROHM_HIP_LIB without touching the shipped librohm_hip.so)."""
+def build(force=False, verbose=True, out=None):
+    """Build the library; `out` builds a second copy (selected with ROHM_HIP_LIB) without touching the shipped librohm_hip.so."""
     target = out or LIB
-    if diag is None:
-        diag = os.environ.get('ROHM_DIAG') == '1'
     if not force and out is None and not is_stale():
         return LIB
     hipcc = find_hipcc()
@@ -56,8 +53,6 @@ def build(force=False, verbose=True, out=None, diag=None):
     import concurrent.futures
     import tempfile
     flags = [f'--offload-arch={ARCH}', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result']
-    if diag:      # diagnostic GEMM variants / knobs for scripts/gemm_*.py (never shipped)
-        flags.append('-DROHM_GEMM_DIAGNOSTICS')
     with tempfile.TemporaryDirectory(prefix='rohm_build_') as tmp:
         objs = [os.path.join(tmp, os.path.basename(f) + '.o') for f in sources()]
 
@@ -78,8 +73,5 @@ def build(force=False, verbose=True, out=None, diag=None):
 
 
 if __name__ == '__main__':
-    if '--diag' in sys.argv:      # second copy with the diagnostic GEMM variants, next to the shipped library
-        print(build(force=True, out=os.path.join(HERE, 'librohm_hip_diag.so'), diag=True))
-    else:
-        build(force='--force' in sys.argv)
-        print(LIB)
+    build(force='--force' in sys.argv)
+    print(LIB)

@@ -118,16 +118,12 @@ __device__ __forceinline__ void attention_item(const float* __restrict__ qkv, fl
             at_dma16<AUX>(vg + (size_t)(2 * piece + half_row) * ldq + (cphys << 2), Vs + piece * 256);
         }
     };
-    // Issue order behind Q and the first key group.  AT_KFIRST (default): K1, K2 | V0, V1 | V2 -- all of K ahead of all of V;
-    // AT_KFIRST=0: the round-2 order K1, V0 | K2, V1 | V2.  Measured (profiles/r5_a_attn_split_timeline.txt): the kernel is not
-    // gated by the arrival of the later key groups in either order (their stamps follow the previous group's 96 MFMAs), the K-first
-    // order is 0.7 % (B = 32) / 1.5 % (B = 64) faster.
-#ifndef AT_KFIRST
-#define AT_KFIRST 1
-#endif
+    // Issue order behind Q and the first key group: K1, K2 | V0, V1 | V2 -- all of K ahead of all of V.  Measured against the
+    // round-2 order K1, V0 | K2, V1 | V2 (profiles/r5_a_attn_split_timeline.txt): the kernel is not gated by the arrival of the
+    // later key groups in either order (their stamps follow the previous group's 96 MFMAs), the K-first order is 0.7 % (B = 32) /
+    // 1.5 % (B = 64) faster.
     issue_k(1);
-    if constexpr (AT_KFIRST != 0) issue_k(2);
-    else issue_v(0);
+    issue_k(2);
 
     // ---- QK^T of the owned block, one 48-key group at a time as K lands ----------------------------------------
     f32x4 sacc[NPASS][AT_NB];
@@ -137,27 +133,16 @@ __device__ __forceinline__ void attention_item(const float* __restrict__ qkv, fl
         for (int kb = 0; kb < AT_NB; ++kb) sacc[ps][kb] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int G = 0; G < 3; ++G) {
-        // (vmcnt retires in issue order)
-        if constexpr (AT_KFIRST != 0) {              // issue order: Q, K0 | K1, K2 | V0, V1 | V2
-            if (G == 0) {
-                AT_WAIT_VM(2 * NKP);                 // K0 landed; K1, K2 may be in flight
-            } else if (G == 1) {
-                issue_v(0);
-                issue_v(1);
-                AT_WAIT_VM(NKP + 2 * NV3);           // K1 landed; K2, V0, V1 in flight
-            } else {
-                issue_v(2);
-                AT_WAIT_VM(3 * NV3);                 // K2 landed; V0, V1, V2 in flight
-            }
-        } else if (G == 0) {                         // issue order: Q, K0 | K1, V0 | K2, V1 | V2
-            AT_WAIT_VM(NKP + NV3);                   // K0 landed; K1, V0 may be in flight
+        // (vmcnt retires in issue order)  issue order: Q, K0 | K1, K2 | V0, V1 | V2
+        if (G == 0) {
+            AT_WAIT_VM(2 * NKP);                     // K0 landed; K1, K2 may be in flight
         } else if (G == 1) {
-            issue_k(2);
+            issue_v(0);
             issue_v(1);
-            AT_WAIT_VM(NV3 + NKP + NV3);             // K1 landed; V0, K2, V1 in flight
+            AT_WAIT_VM(NKP + 2 * NV3);               // K1 landed; K2, V0, V1 in flight
         } else {
             issue_v(2);
-            AT_WAIT_VM(2 * NV3);                     // K2 (and V0) landed; V1, V2 in flight
+            AT_WAIT_VM(3 * NV3);                     // K2 landed; V0, V1, V2 in flight
         }
         __builtin_amdgcn_s_barrier();
         AT_STAMP(2 + G);

@@ -119,19 +119,8 @@ struct GemmParams {
     // centre tap -- their tiles contract over the res_nk chunks starting at K offset res_k0 only, split res_ksplit ways (their slabs
     // are slabs 0 .. res_ksplit - 1 of `partial`; res_ksplit <= 1: they finish in the launch and store to C).  0 = off.
     int res_col0, res_ksplit, res_k0, res_nk;
-    // ---- LayerNorm folded into the GEMMs around it (posenet.hip).  A producer (bias+residual epilogue) writes
-    // per-row partial sums of its OUTPUT, one (sum, sum of squares) pair per column tile: out_stats[m][tile_n][2].
-    // A consumer whose normalised operand is LN(x) = (x - mu) rstd gamma + beta runs on the RAW x with
-    // gamma-scaled weights and finishes in the epilogue:  (acc - mu_m c_n) rstd_m + d_n,  c_n = sum_k gamma_k W_nk,
-    // d_n = bias_n + sum_k beta_k W_nk  (passed as `ln_c` and `bias`).  For EPI_OUT_T the normalised operand is the
-    // column side (tokens): (acc - mu_n c_m) rstd_n + d_m.  A residual that is itself LN(raw) is normalised on the
-    // fly from `r_stats` / `r_gamma` / `r_beta`.  Stats cover ln_dim columns; parts = number of partial pairs.
-    const float* ln_stats; int ln_parts; const float* ln_c;
-    const float* r_stats; int r_parts; const float* r_gamma; const float* r_beta;
-    float* out_stats; int out_parts;
-    int ln_dim; float ln_eps;
     // ---- LayerNorm INSIDE the producer (EPI_BIAS_RES_LN; post-norm nn.TransformerEncoderLayer, model/posenet.py:63-69:
-    // x = norm(x + sublayer(x))).  The N / BN column tiles of a row tile run at the same time on CUs of ONE XCD (the kernel's own
+    // x = norm(x + sublayer(x))).  LN(x) = (x - mu) / sqrt(var + ln_eps) * ln_gamma + ln_beta over ln_dim (= N) columns.  The N / BN column tiles of a row tile run at the same time on CUs of ONE XCD (the kernel's own
     // block -> tile map); each publishes its 144 per-row (mean, M2) pairs in xln_stats[row tile][column tile][144][4]
     // as (mean, tag, M2, tag) with ONE 16-byte store per row, polls the partner tiles' slots until they carry this
     // launch's tag (unique per launch, below), merges the pairs by Chan's update in a fixed tree over the tile index (every tile gets
@@ -141,6 +130,7 @@ struct GemmParams {
     // Tag of a launch = xln_epoch (host: salt + launch index within a pass) + 64 x *xln_pass (device word, incremented by the first
     // kernel of every pass): recordable into a hipGraph, a replay draws fresh tags.  xln_fault != 0: test hook, column tile 0
     // publishes under a wrong tag so that its partners' waits expire.
+    int ln_dim; float ln_eps;
     const float* ln_gamma; const float* ln_beta;
     float* xln_stats; unsigned* xln_err; unsigned xln_epoch; const unsigned* xln_pass; int xln_fault;
     unsigned* xln_xcc;      // [tiles_m][8]: XCD id + 1 of the workgroup that ran each tile (diagnostic: the tests assert the co-location)
@@ -201,9 +191,9 @@ struct ChainParams {
     unsigned long long* flags;
     int fault;      // test hook: bit 0 / 1 sabotage the first / second LayerNorm exchange of the launch
 };
-// ---- ... and the whole encoder stack as one launch: per layer  attention (one head, or half of one, per workgroup of the clip) ->
-// the chain above, the layers looped inside the kernel.  qkv holds layer 0's projection on entry (its own launch); h the embedded
-// tokens; on return h = the encoder's output.  n_head must be 4.  flags: encoder_chain_flag_bytes(M).
+// ---- ... and the whole encoder stack as one launch: the input embedding and layer 0's in-projection, then per layer  attention (one
+// head, or half of one, per workgroup of the clip) -> the chain above, the layers looped inside the kernel.  On return h = the
+// encoder's output.  n_head must be 4.  flags: encoder_chain_flag_bytes(M).
 struct StackLayerW { const float *out_w, *out_b, *n1_w, *n1_b, *l1_w, *l1_b, *l2_w, *l2_b, *n2_w, *n2_b, *in_w, *in_b; };
 struct StackParams {
     float *h, *y, *ff, *qkv, *ctx;
@@ -213,21 +203,22 @@ struct StackParams {
     unsigned long long* flags;
     int fault;
     StackLayerW layer[8];      // in_w / in_b of layer l feed the phase that closes layer l - 1
-    // front != 0: the launch starts from the packed input instead of from (h, qkv of layer 0): two leading phases per clip,
-    //   h = InputProcess embedding (EPI_EMBED's arithmetic: A = apack [M, lda_pack] over k_embed columns, W = w_embed [D, ldw_embed],
-    //   + positional / timestep table rows) and qkv = in_proj_0(h) -- model/posenet.py:85-92 up to the first encoder layer.
-    int front;
+    // The launch starts from the packed input: two leading phases per clip, h = InputProcess embedding (EPI_EMBED's arithmetic:
+    // A = apack [M, lda_pack] over k_embed columns, W = w_embed [D, ldw_embed], + positional / timestep table rows) and
+    // qkv = in_proj_0(h) -- model/posenet.py:85-92 up to the first encoder layer.
     const float* apack; int lda_pack; const float* w_embed; int ldw_embed; int k_embed;
     int S; const float* tab; const float* tab0; int ldtab, ldtab0, tab_by_row;
     // Diagnostics (null on every product path): when set, lane 0 of every workgroup stamps the 100 MHz wall clock (s_memrealtime) at the
     // seams of its phases into timeline[(block * kStackTimelineLayers + layer) * kStackTimelineStamps + k]
     // (rohm_posenet_set_stack_timeline; scripts/stack_timeline.py turns the stamps into per-phase spans and the in-stack attention rate).
     unsigned long long* timeline;
-    // tail != 0 (sampling loop, single-round launches only): the launch does not end with the encoder's output but carries on, per clip,
+    // tail != 0 (sampling loop): the launch does not end with the encoder's output but carries on, per clip,
     // with OutputProcess (model/heads.py:171-176: x0[:, traj:] = h . Wout^T + bout, x0[:, :traj] = cond[:, :traj], model/posenet.py:94-96),
     // the ancestral update x_prev = c1 x0 + c2 x_t + sigma noise (gaussian_diffusion_posenet.py:212-234,426-434) written over x in place,
     // and the x_t half of the NEXT step's token-major pack -- one launch per denoising step.  The 17 x 9 (16 x 16) output blocks of a
-    // clip are dealt to the 16 / 32 waves of its workgroups (<= 10 / 5 blocks per wave).
+    // clip are dealt to the 16 / 32 waves of its workgroups (<= 10 / 5 blocks per wave).  The phase of a clip reads only what the
+    // workgroups of that clip wrote in this launch (its h, behind a meeting of the clip), so any number of rounds of workgroups is
+    // fine (B = 128 runs two).
     int tail;
     const float* t_out_w; const float* t_out_b;      // [c_out, D], [c_out]
     float* t_x; const float* t_cond; const float* t_noise;      // [B, C, 1, T]; noise may be null (sigma == 0)
@@ -291,10 +282,6 @@ __device__ __forceinline__ float gelu_erf(float x) {
 // ---- other kernels -----------------------------------------------------------------------
 int launch_layernorm(float* x, const float* g, const float* b, int M, int D, hipStream_t s);
 int launch_attention(const float* qkv, float* ctx, int n_seq, int n_head, int n_tok, int head_dim, hipStream_t s);
-// Graph-replayable variants: per-step values come from device tables indexed by a device-side step counter.
-int launch_ddpm_step_indexed(const float* x_t, const float* x0, const float* noise_base, const float* coef_tab,
-                             const int* step_ctr, float* out, size_t n, hipStream_t s);
-int launch_advance_counter(int* step_ctr, hipStream_t s);
 int launch_ddpm_step(const float* x_t, const float* x0, const float* noise, const float* grad, float c1,
                      float c2, float sigma, float gscale, float* out, size_t n, hipStream_t s);
 

@@ -37,11 +37,7 @@ constexpr int kMaxBN = 384;
 // the statistics / bias-row zone -- so that the next phase's weight chunks can land while this phase's epilogue still uses its zone
 constexpr int kZone = 2 * (BM + kMaxBN) * BK;                          // float offset
 constexpr int kLdsFloats = kZone + 512 + 4 * BM * 2;
-#ifdef ROHM_CHAIN_NO_SC1      // TIMING experiments only (results may be stale): what does the device-scope policy of the operand loads cost?
-constexpr int kSc1 = 0;
-#else
 constexpr int kSc1 = 16;                                               // cache policy of a load that must come from L2 (device scope)
-#endif
 
 struct PhaseArgs {
     const float* A; int lda;
@@ -84,16 +80,11 @@ __device__ __forceinline__ void group_sync(unsigned long long* flags, int tn, in
     __syncthreads();
     // The flag by a PLAIN 8-byte store: it stays in the XCD's L2, where the partners' device-scope polls are served.  A device-scope (sc1)
     // store writes through to the memory side and drops the line from L2, so every poll pays the trip out (measured in
-    // csrc/trajnet_resident.hip: 2.0 -> 1.2 us per 32-partner meeting; here -DROHM_CHAIN_FLAG_SC1 builds the old form for A/B runs).
+    // csrc/trajnet_resident.hip: 2.0 -> 1.2 us per 32-partner meeting).
     if (tid == 0) {
-#ifdef ROHM_CHAIN_FLAG_SC1
-        __hip_atomic_store(flags + tn, ((unsigned long long)xcc1 << 32) | tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
         flags[tn] = ((unsigned long long)xcc1 << 32) | tag;
         asm volatile("" ::: "memory");
-#endif
     }
-#ifndef ROHM_CHAIN_NO_MEET      // TIMING experiment only (results may be stale): what do the meetings cost?
     if (tid < G && tid != tn) {
         for (int it = 0;; ++it) {
             const unsigned long long f = __hip_atomic_load(flags + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -101,9 +92,7 @@ __device__ __forceinline__ void group_sync(unsigned long long* flags, int tn, in
                 if ((unsigned)(f >> 32) != xcc1) __hip_atomic_store(err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 break;
             }
-#ifndef ROHM_CHAIN_NO_SLEEP
             __builtin_amdgcn_s_sleep(1);
-#endif
             if ((it & 127) == 127 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
             if (it > (1 << 19)) {
                 __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -111,7 +100,6 @@ __device__ __forceinline__ void group_sync(unsigned long long* flags, int tn, in
             }
         }
     }
-#endif
     __syncthreads();
     // No acquire fence here: at agent scope it is `buffer_inv sc1`, which on this multi-XCD part also drops the L2's lines of ordinary
     // memory -- weights and activations come back from HBM, measured +5 us per meeting (gemm_chain 322 -> 344 us per layer,
@@ -130,17 +118,11 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
     // Every phase on v_mfma_f32_16x16x4_f32.  gemm_f32.hip's own launches run rows 0..127 of their 256- / 384-wide tiles on
     // v_mfma_f32_32x32x2_f32 (half the operand-register traffic per flop; measured faster there in round 2); INSIDE the stack the
     // all-16x16 form is the faster one: same box, two legs each, 22.36 -> 22.70 clips/s, stack launch 2812 -> 2773 us
-    // (profiles/r5_j_*).  -DROHM_CHAIN_M32 builds the mixed form for A/B runs.
-#ifdef ROHM_CHAIN_M32
-    constexpr bool M32 = WN >= 64;
-#else
-    constexpr bool M32 = false;
-#endif
-    constexpr int NCB = WN / 16, NCB32 = WN / 32;
+    // (profiles/r5_j_*).
+    constexpr int NCB = WN / 16;
     constexpr int B_ITERS = BN * 8 / 256;
     constexpr int PIECES = A_ITERS + B_ITERS;
     constexpr int AUX = SC1 ? kSc1 : 0;
-    static_assert(!(EPI == EPI_BIAS_RES_LN && M32), "the LayerNorm tail exists for the 16x16 layouts (BN <= 128)");
 
     float* As = smem;
     float* Bs = smem + 2 * BM * BK;
@@ -150,7 +132,6 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int li = lane & 15, lg = lane >> 4;
-    const int li32 = lane & 31, lg32 = lane >> 5;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave) * 64;
     const int m0 = p.m0, n0 = p.n0;
 
@@ -181,106 +162,43 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
                                              (__attribute__((address_space(3))) void*)dst, 16, 0, AUX);
         }
     };
-#ifdef ROHM_CHAIN_W_DEAD64        // TIMING experiment only (WRONG results): the 64-wide tiles' weight chunks as ordinary global loads into registers
-    f32x4 wdead[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};      // that nobody multiplies: what does the register path cost to ISSUE?
-#endif
     auto dma_b = [&](int buf, int k0) {
-#ifdef ROHM_CHAIN_NO_W_DMA64      // TIMING experiment only (WRONG results: stale weights in LDS): what would taking W off the LDS-DMA path of the 64-wide tiles buy?
-        if constexpr (BN == 64) return;
-#endif
-#ifdef ROHM_CHAIN_W_DEAD64
-        if constexpr (BN == 64) {
-            asm volatile("" ::"v"(wdead[0]), "v"(wdead[1]));      // "use" of the previous chunk's loads (they have landed: vmcnt(0) + barrier just above)
-#pragma unroll
-            for (int i = 0; i < B_ITERS; ++i) wdead[i] = *reinterpret_cast<const f32x4*>(b_src[i] + k0);
-            return;
-        }
-#endif
 #pragma unroll
         for (int i = 0; i < B_ITERS; ++i)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_src[i] + k0),
                                              (__attribute__((address_space(3))) void*)(Bs + buf * (BN * BK) + (i * 256 + wave_u) * 4), 16, 0, 0);
     };
 
-    // ---- accumulators and fragments (gemm_f32.hip's layouts) ---------------------------------------------------------------------
-    constexpr int N32 = M32 ? 4 * NCB32 : 1;
-    constexpr int N16 = M32 ? NCB : NRB * NCB;
-    f32x16c acc32[N32];
-    f32x4 acc16[N16];
+    // ---- accumulators and fragments (gemm_f32.hip's 16x16 layouts) ---------------------------------------------------------------
+    f32x4 acc16[NRB * NCB];
 #pragma unroll
-    for (int i = 0; i < N32; ++i)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc32[i][q] = 0.f;
-#pragma unroll
-    for (int i = 0; i < N16; ++i) acc16[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    constexpr int FA = M32 ? 9 : NRB;
-    constexpr int FB = M32 ? 2 * NCB32 + NCB : NCB;
-    constexpr int READS = FA + FB;
-    constexpr int MFMAS = M32 ? 32 * NCB32 + 4 * NCB : 4 * NRB * NCB;
-    struct Frag { f32x4 a[FA]; f32x4 b[FB]; };
+    for (int i = 0; i < NRB * NCB; ++i) acc16[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    constexpr int READS = NRB + NCB;
+    constexpr int MFMAS = 4 * NRB * NCB;
+    struct Frag { f32x4 a[NRB]; f32x4 b[NCB]; };
     Frag f0, f1;
     auto read_frags = [&](Frag& f, int buf, int ks) {
         const float* as = As + buf * (BM * BK);
         const float* bs = Bs + buf * (BN * BK) + wave * WN * BK;
-        if constexpr (M32) {
+        const int slot = ks * 4 + lg;
 #pragma unroll
-            for (int s8 = 0; s8 < 2; ++s8) {
-                const int slot = ks * 4 + s8 * 2 + lg32;
+        for (int c = 0; c < NCB; ++c) f.b[c] = *reinterpret_cast<const f32x4*>(bs + lds_off(c * 16 + li, slot));
 #pragma unroll
-                for (int cb = 0; cb < NCB32; ++cb)
-                    f.b[s8 * NCB32 + cb] = *reinterpret_cast<const f32x4*>(bs + lds_off(cb * 32 + li32, slot));
-#pragma unroll
-                for (int rb = 0; rb < 4; ++rb)
-                    f.a[s8 * 4 + rb] = *reinterpret_cast<const f32x4*>(as + lds_off(rb * 32 + li32, slot));
-            }
-            const int slot16 = ks * 4 + lg;
-            f.a[8] = *reinterpret_cast<const f32x4*>(as + lds_off(128 + li, slot16));
-#pragma unroll
-            for (int c = 0; c < NCB; ++c)
-                f.b[2 * NCB32 + c] = *reinterpret_cast<const f32x4*>(bs + lds_off(c * 16 + li, slot16));
-        } else {
-            const int slot = ks * 4 + lg;
-#pragma unroll
-            for (int c = 0; c < NCB; ++c) f.b[c] = *reinterpret_cast<const f32x4*>(bs + lds_off(c * 16 + li, slot));
-#pragma unroll
-            for (int r = 0; r < NRB; ++r) f.a[r] = *reinterpret_cast<const f32x4*>(as + lds_off(r * 16 + li, slot));
-        }
+        for (int r = 0; r < NRB; ++r) f.a[r] = *reinterpret_cast<const f32x4*>(as + lds_off(r * 16 + li, slot));
     };
     auto mma_half = [&](const Frag& f) {      // weights on the MFMA "A" side: a lane ends with 4 consecutive output columns
-        if constexpr (M32) {
 #pragma unroll
-            for (int s8 = 0; s8 < 2; ++s8)
+        for (int r = 0; r < NRB; ++r)
+#pragma unroll
+            for (int c = 0; c < NCB; ++c)
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-                        for (int cb = 0; cb < NCB32; ++cb)
-                            acc32[rb * NCB32 + cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.b[s8 * NCB32 + cb][j], f.a[s8 * 4 + rb][j],
-                                                                                          acc32[rb * NCB32 + cb], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int c = 0; c < NCB; ++c)
-                    acc16[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.b[2 * NCB32 + c][j], f.a[8][j], acc16[c], 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int r = 0; r < NRB; ++r)
-#pragma unroll
-                for (int c = 0; c < NCB; ++c)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc16[r * NCB + c] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.b[c][j], f.a[r][j], acc16[r * NCB + c], 0, 0, 0);
-        }
+                    acc16[r * NCB + c] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.b[c][j], f.a[r][j], acc16[r * NCB + c], 0, 0, 0);
     };
 
     // ---- prologue -----------------------------------------------------------------------------------------------------------
     const int nk = p.K / BK;                       // >= 16 here
-#ifdef ROHM_CHAIN_NO_COL_LDS      // experiment builds: with the all-16x16 form a 384-wide tile has 6 column groups per lane, not 18
-    constexpr bool COL_LDS = false;
-#else
     constexpr bool COL_LDS = BN >= 384;            // the 384-wide tile takes its bias row through LDS (gemm_f32.hip's choice for that width)
-#endif
     if constexpr (!PREF) { dma_b(0, 0); dma_b(1, BK); }
     if constexpr (COL_LDS) {
         if (wave == 0) {
@@ -298,21 +216,14 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
 
     // ---- epilogue operands (requested at the top of the peeled last chunk: they land under its MFMAs) --------------------------
     const int nw = n0 + wave * WN;
-#ifdef ROHM_CHAIN_NO_COL_LDS
-    constexpr bool COL_LDS_TILE = false;
-#else
-    constexpr bool COL_LDS_TILE = BN >= 384;       // (= COL_LDS of the prologue: its bias row comes from LDS, nothing to request early)
-#endif
     struct ColOps { f32x4 bias, g4, b4; };
     constexpr bool RES = (EPI == EPI_BIAS_RES_LN);
     constexpr bool HAS_RES = RES || EPI == EPI_EMBED;      // a per-unit operand from memory: the residual, or the table row of the embedding
     // the last chunk's iteration is peeled (no wait / barrier / prefetch in it, the epilogue's operands requested at its top) for tiles up to
-    // ROHM_CHAIN_PEEL_MAX columns: 256 like gemm_f32.hip (measured: peeling the 384-wide tile too loses 0.6 %, profiles/r5_k_*)
-#ifndef ROHM_CHAIN_PEEL_MAX
-#define ROHM_CHAIN_PEEL_MAX 256
-#endif
-    constexpr bool PEEL = BN <= ROHM_CHAIN_PEEL_MAX;
-    constexpr bool EARLY = PEEL && !COL_LDS_TILE;
+    // 256 columns like gemm_f32.hip (measured: peeling the 384-wide tile too loses 0.6 %, profiles/r5_k_*).  The 384-wide tile's bias
+    // row comes from LDS: nothing to request early there.
+    constexpr bool PEEL = BN <= 256;
+    constexpr bool EARLY = PEEL && !COL_LDS;
     const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
     auto load_col = [&](int nb) __attribute__((always_inline)) {
         ColOps o{zero4, zero4, zero4};
@@ -325,53 +236,20 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
         }
         return o;
     };
-    constexpr int NUNIT = M32 ? 16 * NCB32 + NCB : NCB * NRB;
-    constexpr int NCG = M32 ? 4 * NCB32 + NCB : NCB;
     auto for_units = [&](auto&& fn) __attribute__((always_inline)) {
-        if constexpr (M32) {
+        // row-major over the lane's units: the NCB 64-byte pieces of a row's WN columns are stored by consecutive instructions, so
+        // the halves of a 128-byte line reach L2 together (column-major order -- gemm_f32.hip's -- left 9 stores between them and
+        // the wide tiles' HBM-side write traffic 20 % above the algorithmic, profiles/r5_n_pmc_traffic.txt)
 #pragma unroll
-            for (int rb = 0; rb < 4; ++rb)
+        for (int r = 0; r < NRB; ++r)
 #pragma unroll
-                for (int cb = 0; cb < NCB32; ++cb)
-#pragma unroll
-                    for (int qq = 0; qq < 4; ++qq) {
-                        const f32x16c& a = acc32[rb * NCB32 + cb];
-                        fn((rb * NCB32 + cb) * 4 + qq, cb * 4 + qq, m0 + rb * 32 + li32, nw + cb * 32 + 8 * qq + 4 * lg32,
-                           f32x4{a[4 * qq], a[4 * qq + 1], a[4 * qq + 2], a[4 * qq + 3]});
-                    }
-#pragma unroll
-            for (int c = 0; c < NCB; ++c) fn(16 * NCB32 + c, 4 * NCB32 + c, m0 + 128 + li, nw + c * 16 + lg * 4, acc16[c]);
-        } else {
-            // row-major over the lane's units: the NCB 64-byte pieces of a row's WN columns are stored by consecutive instructions, so
-            // the halves of a 128-byte line reach L2 together (column-major order -- gemm_f32.hip's -- left 9 stores between them and
-            // the wide tiles' HBM-side write traffic 20 % above the algorithmic, profiles/r5_n_pmc_traffic.txt)
-#ifndef ROHM_CHAIN_STORE_COLMAJOR
-#pragma unroll
-            for (int r = 0; r < NRB; ++r)
-#pragma unroll
-                for (int c = 0; c < NCB; ++c) fn(c * NRB + r, c, m0 + r * 16 + li, nw + c * 16 + lg * 4, acc16[r * NCB + c]);
-#else
-#pragma unroll
-            for (int c = 0; c < NCB; ++c)
-#pragma unroll
-                for (int r = 0; r < NRB; ++r) fn(c * NRB + r, c, m0 + r * 16 + li, nw + c * 16 + lg * 4, acc16[r * NCB + c]);
-#endif
-        }
+            for (int c = 0; c < NCB; ++c) fn(c * NRB + r, c, m0 + r * 16 + li, nw + c * 16 + lg * 4, acc16[r * NCB + c]);
     };
-    ColOps col[NCG];
-    f32x4 res[HAS_RES ? NUNIT : 1];
+    ColOps col[NCB];
+    f32x4 res[HAS_RES ? NCB * NRB : 1];
     auto request_ops = [&]() __attribute__((always_inline)) {
-        if constexpr (M32) {
 #pragma unroll
-            for (int cb = 0; cb < NCB32; ++cb)
-#pragma unroll
-                for (int qq = 0; qq < 4; ++qq) col[cb * 4 + qq] = load_col(nw + cb * 32 + 8 * qq + 4 * lg32);
-#pragma unroll
-            for (int c = 0; c < NCB; ++c) col[4 * NCB32 + c] = load_col(nw + c * 16 + lg * 4);
-        } else {
-#pragma unroll
-            for (int c = 0; c < NCB; ++c) col[c] = load_col(nw + c * 16 + lg * 4);
-        }
+        for (int c = 0; c < NCB; ++c) col[c] = load_col(nw + c * 16 + lg * 4);
         if constexpr (RES)
             for_units([&](int i, int, int m, int nb, f32x4) __attribute__((always_inline)) {
                 res[i] = *reinterpret_cast<const f32x4*>(p.R + (size_t)m * p.ldr + nb);
@@ -452,14 +330,6 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
 #pragma unroll
                 for (int q = 0; q < 4; ++q) a[q] = (a[q] + col[c].bias[q]) + rr[q];
             }
-#ifdef ROHM_CHAIN_NO_LN_EPI      // TIMING experiment only (WRONG results: no LayerNorm): what does the LayerNorm part of the epilogue cost?
-#pragma unroll
-        for (int r = 0; r < NRB; ++r)
-#pragma unroll
-            for (int c = 0; c < NCB; ++c)
-                *reinterpret_cast<f32x4*>(p.C + (size_t)(m0 + r * 16 + li) * p.ldc + nw + c * 16 + lg * 4) = acc16[r * NCB + c];
-        return;
-#endif
         typedef unsigned rohm_u2 __attribute__((ext_vector_type(2)));
         auto merge_swap = [](float& m, float& q2, float n, bool far) __attribute__((always_inline)) {
             rohm_u2 tm, tq;
@@ -538,9 +408,6 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
                     if (!same_xcd) __hip_atomic_store(p.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     break;
                 }
-#ifdef ROHM_CHAIN_NO_LN_WAIT      // TIMING experiment only (WRONG statistics: whatever the slots hold): what does waiting for the partners' statistics cost?
-                break;
-#endif
                 __builtin_amdgcn_s_sleep(1);
                 if ((it & 127) == 127 && __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
                 if (it > (1 << 19)) {
@@ -589,12 +456,10 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
             f32x4 v;
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] = a[q] + col[cg].bias[q];
-#ifndef ROHM_CHAIN_NO_GELU      // TIMING experiment only (WRONG results): what does the erf-form GELU cost in linear1's epilogue?
             if constexpr (EPI == EPI_BIAS_GELU) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = gelu_erf(v[q]);
             }
-#endif
             if constexpr (EPI == EPI_QKV) {
                 if (nb < p.qcols) {
 #pragma unroll
@@ -869,7 +734,7 @@ __global__ __launch_bounds__(256) void encoder_chain_kernel(ChainParams p) {
 // Workgroup (clip g, part tn) computes, per layer, head tn (G = 4: a whole (clip, head) item on four waves, two owned query blocks
 // per wave) or half tn & 1 of head tn >> 1 (G = 8: the SPLIT shape of attention_f32.hip), then its column tile of every GEMM phase.
 // Every operand another workgroup wrote earlier in THIS launch is fetched past the L1 (sc1 LDS-DMA): the same addresses were read one
-// layer earlier.  With front != 0 two leading phases turn the packed input into h and layer 0's qkv first (InputProcess + in_proj_0).
+// layer earlier.  Two leading phases turn the packed input into h and layer 0's qkv first (InputProcess + in_proj_0).
 template <int G>
 __global__ __launch_bounds__(256) void encoder_stack_kernel(StackParams p) {
     using namespace chain;
@@ -893,25 +758,25 @@ __global__ __launch_bounds__(256) void encoder_stack_kernel(StackParams p) {
     auto stamp = [&](int layer, int k) __attribute__((always_inline)) {
         if (tl != nullptr && threadIdx.x == 0) tl[layer * kStackTimelineStamps + k] = __builtin_amdgcn_s_memrealtime();
     };
-    if (p.front) {
-        // ---- E: h = [x_t | cond] . We^T + table rows;  D0: qkv = in_proj_0(h) -- flags of "layer" 8 ------------------------------------
-        int tid = tid0;
-        asm volatile("" : "+v"(tid));
-        const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6) * 64;
-        unsigned long long* const fl = p.flags + ((size_t)g * 9 + 8) * 5 * 8;
-        a.A = p.apack; a.lda = p.lda_pack; a.W = p.w_embed; a.ldw = p.ldw_embed; a.C = p.h; a.ldc = p.D; a.K = p.k_embed; a.n0 = tn * BNL;
-        a.S = p.S; a.tab = p.tab; a.tab0 = p.tab0; a.ldtab = p.ldtab; a.ldtab0 = p.ldtab0; a.tab_by_row = p.tab_by_row;
-        stamp(8, 0);
-        gemm_phase<BNL, EPI_EMBED, false, false, G == 8>(a, smem, tid, [&]() { prefetch_w<BNQ>(p.layer[0].in_w, p.D, tn * BNQ, smem, tid, wave_u); });
-        stamp(8, 1);
-        group_sync(fl, tn, G, ep, xcc1, p.xln_err, tid);
-        stamp(8, 2);
-        a.A = p.h; a.lda = p.D; a.W = p.layer[0].in_w; a.ldw = p.D; a.C = p.qkv; a.ldc = 3 * p.D; a.K = p.D; a.bias = p.layer[0].in_b;
-        a.n0 = tn * BNQ;
-        gemm_phase<BNQ, EPI_QKV, true, true, G == 8>(a, smem, tid, []() {});
-        stamp(8, 3);
-        group_sync(fl + 8, tn, G, ep, xcc1, p.xln_err, tid);
-        stamp(8, 4);
+    {
+    // ---- E: h = [x_t | cond] . We^T + table rows;  D0: qkv = in_proj_0(h) -- flags of "layer" 8 ------------------------------------
+    int tid = tid0;
+    asm volatile("" : "+v"(tid));
+    const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6) * 64;
+    unsigned long long* const fl = p.flags + ((size_t)g * 9 + 8) * 5 * 8;
+    a.A = p.apack; a.lda = p.lda_pack; a.W = p.w_embed; a.ldw = p.ldw_embed; a.C = p.h; a.ldc = p.D; a.K = p.k_embed; a.n0 = tn * BNL;
+    a.S = p.S; a.tab = p.tab; a.tab0 = p.tab0; a.ldtab = p.ldtab; a.ldtab0 = p.ldtab0; a.tab_by_row = p.tab_by_row;
+    stamp(8, 0);
+    gemm_phase<BNL, EPI_EMBED, false, false, G == 8>(a, smem, tid, [&]() { prefetch_w<BNQ>(p.layer[0].in_w, p.D, tn * BNQ, smem, tid, wave_u); });
+    stamp(8, 1);
+    group_sync(fl, tn, G, ep, xcc1, p.xln_err, tid);
+    stamp(8, 2);
+    a.A = p.h; a.lda = p.D; a.W = p.layer[0].in_w; a.ldw = p.D; a.C = p.qkv; a.ldc = 3 * p.D; a.K = p.D; a.bias = p.layer[0].in_b;
+    a.n0 = tn * BNQ;
+    gemm_phase<BNQ, EPI_QKV, true, true, G == 8>(a, smem, tid, []() {});
+    stamp(8, 3);
+    group_sync(fl + 8, tn, G, ep, xcc1, p.xln_err, tid);
+    stamp(8, 4);
     }
 #pragma unroll 1
     for (int l = 0; l < p.L; ++l) {
@@ -979,8 +844,8 @@ int launch_encoder_stack(const StackParams& p, hipStream_t s) {
     ROHM_ARG_CHECK(G != 0 && p.n_head == 4 && p.L >= 1 && p.L <= 8, "encoder_stack: shape (M %d, D %d, F %d, %d heads, %d layers) has no stack form",
                    p.M, p.D, p.F, p.n_head, p.L);
     ROHM_ARG_CHECK(p.h && p.y && p.ff && p.qkv && p.ctx && p.xln_stats && p.xln_err && p.xln_pass && p.xln_xcc && p.flags, "encoder_stack: null operand");
-    ROHM_ARG_CHECK(!p.front || (p.apack && p.w_embed && p.tab && p.tab0 && p.S == chain::BM && p.k_embed >= 2 * chain::BK && p.k_embed % chain::BK == 0 &&
-                                p.lda_pack % 4 == 0 && p.ldw_embed % 4 == 0 && p.ldtab % 4 == 0 && p.ldtab0 % 4 == 0),
+    ROHM_ARG_CHECK(p.apack && p.w_embed && p.tab && p.tab0 && p.S == chain::BM && p.k_embed >= 2 * chain::BK && p.k_embed % chain::BK == 0 &&
+                       p.lda_pack % 4 == 0 && p.ldw_embed % 4 == 0 && p.ldtab % 4 == 0 && p.ldtab0 % 4 == 0,
                    "encoder_stack: bad operands of the leading embed phase");
     StackParams q = p;
     q.tiles_m = p.M / chain::BM;
@@ -999,9 +864,9 @@ int launch_encoder_stack(const StackParams& p, hipStream_t s) {
         attr_set[dev][G == 8] = true;
     }
     const double MM = (double)p.M, D = p.D, F = p.F, L = p.L;
-    // algorithmic work of the launch: L x (attention 4 S^2 d_h per (clip, head) + out-proj + FF1 + FF2) + (L - 1) QKV projections
-    const double flops = L * (4.0 * 144.0 * 128.0 * MM * p.n_head + 2.0 * MM * (D * D + 2.0 * D * F)) + (L - 1.0 + (p.front ? 1.0 : 0.0)) * 2.0 * MM * 3.0 * D * D +
-                         (p.front ? 2.0 * MM * D * p.k_embed : 0.0);
+    // algorithmic work of the launch: L x (attention 4 S^2 d_h per (clip, head) + out-proj + FF1 + FF2 + QKV projection) + the embedding
+    const double flops = L * (4.0 * 144.0 * 128.0 * MM * p.n_head + 2.0 * MM * (D * D + 2.0 * D * F)) + L * 2.0 * MM * 3.0 * D * D +
+                         2.0 * MM * D * p.k_embed;
     const double bytes = 4.0 * (L * (MM * (3.0 * D + D + 4.0 * D + 2.0 * F + D) + D * D + 2.0 * D * F) + (L - 1.0) * (MM * 3.0 * D + 3.0 * D * D));
     const double tail_flops = p.tail ? 2.0 * MM * D * (p.t_C - p.t_traj) : 0.0;
     prof::Scope ps(p.tail ? "gemm_stack_tail" : "gemm_stack", flops + tail_flops, bytes, s);

@@ -33,9 +33,7 @@
 //   * epilogue: the operands a unit needs from memory (bias, residual, embed-table row) are read for ALL units before the first store
 //     -- GemmParams members cannot be restrict, so behind a store to C the compiler must re-read them, one vmcnt(0) round trip per
 //     unit -- and, for tiles up to 256 wide, already at the top of the peeled last K chunk (they land under its MFMAs); the 384-wide
-//     tile takes its bias row through LDS.  The FULL instantiation has no conditional operand loads (LayerNorm folding lives in the
-//     general one).
-#include <stdlib.h>
+//     tile takes its bias row through LDS.  The FULL instantiation has no conditional operand loads.
 #include <type_traits>
 #include <string.h>
 #include "common.h"
@@ -52,32 +50,10 @@ constexpr int kSkWorkgroups = 256;  // stream-K launches: one workgroup per CU (
 constexpr int A_UNITS = BM * 8;     // 16-byte units per A chunk (1152)
 constexpr int A_ITERS = (A_UNITS + 255) / 256;  // 5 (the last pass is half populated)
 
-// (mu, rstd) of one row from its partial (sum, sum of squares) pairs -- biased variance, eps inside the root, like
-// nn.LayerNorm.  The pairs of a row are contiguous (parts x 2 floats, parts a multiple of 2): independent 16-byte
-// loads, summed in index order.
-__device__ __forceinline__ void row_mu_rstd(const float* __restrict__ stats, int parts, int row, int dim, float eps,
-                                            float& mu, float& rstd) {
-    const f32x4* sp = reinterpret_cast<const f32x4*>(stats + (size_t)row * parts * 2);
-    f32x4 v[4];                      // parts <= 8 (launch_gemm checks)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (2 * i < parts) ? sp[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-    float s = 0.f, q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { s += v[i][0]; q += v[i][1]; s += v[i][2]; q += v[i][3]; }
-    const float inv = 1.0f / (float)dim;
-    mu = s * inv;
-    const float var = fmaxf(q * inv - mu * mu, 0.f);
-    rstd = 1.0f / sqrtf(var + eps);
-}
-
-#ifndef ROHM_GEMM_MIXED
-#define ROHM_GEMM_MIXED 1
-#endif
-
-template <int BN, int EPI, int VAR = 0, bool FULL = false, bool CONV = false>
+template <int BN, int EPI, bool FULL = false, bool CONV = false>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     constexpr int WN = BN / 4;             // columns per wave
-    constexpr bool M32 = (WN >= 64) && (ROHM_GEMM_MIXED != 0);   // mixed 32x32x2 + 16x16x4 path
+    constexpr bool M32 = WN >= 64;         // mixed 32x32x2 + 16x16x4 path
     constexpr int NCB = WN / 16;           // 16-wide column blocks per wave
     constexpr int NCB32 = WN / 32;         // 32-wide column blocks per wave (M32)
     constexpr int B_UNITS = BN * 8;
@@ -100,8 +76,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     const int li32 = lane & 31, lg32 = lane >> 5;   // 32x32x2 fragment coordinates
     const int wave_u = __builtin_amdgcn_readfirstlane(wave) * 64;   // provably wave-uniform LDS base
 
-    unsigned long long ts_wall[5] = {0, 0, 0, 0, 0}, ts_cyc[2] = {0, 0};   // VAR 7 only (timeline diagnostics)
-    if constexpr (VAR == 7) ts_wall[0] = wall_clock64();
     const int tiles_n = (p.N + BN - 1) / BN;
     const int tiles_m = (p.M + BM - 1) / BM;
     int ksplit = (EPI == EPI_BIAS && p.ksplit > 1) ? p.ksplit : 1;
@@ -116,7 +90,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     // workgroup (role 2: owner) adds the slots of the blocks 8, 16, .. below it that hold the tile's earlier chunks -- same XCD,
     // dispatched EARLIER, written long before -- and runs the epilogue.  Dependencies point to lower block indices only: no
     // workgroup waits for one that may not have started.
-    constexpr bool SK = (EPI == EPI_OUT_T) && !FULL && !CONV && BN == 64 && VAR == 0;
+    constexpr bool SK = (EPI == EPI_OUT_T) && !FULL && !CONV && BN == 64;
     int sk_lo = 0, sk_hi = 0, sk_role = -1;      // role of the current segment: 0 whole tile, 1 producer, 2 owner; -1 before the first
     // Tag of this launch's exchange slots (LayerNorm statistics / stream-K flags): the host's part (a per-handle salt + the launch's
     // index within a network pass) plus 64 x the workspace's pass counter, a DEVICE word that the first kernel of every pass
@@ -347,8 +321,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     };
 
     // ---- main loop -------------------------------------------------------------------------------------------
-    // VAR (diagnostic builds, ROHM_GEMM_VARIANT): 0 = shipped; 5 = MFMA only + no epilogue; 6 = no epilogue;
-    // 7 = shipped schedule + per-workgroup phase timestamps written to p.R (scripts/gemm_timeline.py).
     // split-K: this workgroup owns chunks [kc0, kc0 + nk) of the K / BK chunks (the first K/BK % ksplit splits
     // take one more)
     const int nk = nk_all / ksplit + (split < nk_all % ksplit ? 1 : 0);
@@ -359,7 +331,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     // against the stores to C): two LDS-DMA pieces of wave 0 in front of chunk 0's (older, so the prologue's counted wait covers
     // them; through registers the ds_write drew a vmcnt(0) that drained chunk 1 as well)
     constexpr bool COL_LDS = FULL && !CONV && BN >= 384 && EPI != EPI_EMBED && EPI != EPI_OUT_T;
-    float* const bias_s = lds_dummy + 512;          // the row-statistics zone of the general instantiation (unused here), 4.5 KiB
+    float* const bias_s = lds_dummy + 512;          // the row-statistics zone of EPI_BIAS_RES_LN (unused here), 4.5 KiB
     if constexpr (COL_LDS) {
         if (wave == 0) {
 #pragma unroll
@@ -373,55 +345,23 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     }
     dma(0, kbase);
     if (nk > 1) dma(1, kbase + BK);
-    // ---- LayerNorm folding (common.h): row statistics, fetched under the prologue's DMA latency ----------------------
-    // per-lane row slots -- !M32: slot r = row m0 + 16 r + li; M32: slots 0..3 = rows m0 + 32 rb + li32, slot 4 = row
-    // m0 + 128 + li.
-    constexpr int NSLOT = M32 ? 5 : NRB;
-    // LayerNorm folding (opt-in, measured slower than the LayerNorm kernel) lives in the general instantiation only: the FULL one
-    // carries no run-time choices in its epilogue (every conditional operand load is a value merge the compiler resolves with a
-    // vmcnt(0) right behind the load)
-    constexpr bool LN_CONSUMER = (EPI == EPI_QKV || EPI == EPI_BIAS_GELU) && !FULL;
-    constexpr bool LN_PRODUCER = (EPI == EPI_BIAS_RES) && !M32 && !FULL;
-    float amu[NSLOT], ars[NSLOT], rmu[NSLOT], rrs[NSLOT], osum[NSLOT], osq[NSLOT];
-    auto slot_row = [&](int sl) {
-        int m;
-        if constexpr (M32) m = (sl < 4) ? m0 + sl * 32 + li32 : m0 + 128 + li;
-        else m = m0 + sl * 16 + li;
-        return m < p.M ? m : p.M - 1;
-    };
-    if constexpr (LN_CONSUMER) {
-        if (p.ln_stats) {
-#pragma unroll
-            for (int sl = 0; sl < NSLOT; ++sl)
-                row_mu_rstd(p.ln_stats, p.ln_parts, slot_row(sl), p.ln_dim, p.ln_eps, amu[sl], ars[sl]);
-        }
-    }
-    if constexpr (EPI == EPI_BIAS_RES && !FULL) {
-        if (p.r_stats) {
-#pragma unroll
-            for (int sl = 0; sl < NSLOT; ++sl)
-                row_mu_rstd(p.r_stats, p.r_parts, slot_row(sl), p.ln_dim, p.ln_eps, rmu[sl], rrs[sl]);
-        }
-#pragma unroll
-        for (int sl = 0; sl < NSLOT; ++sl) { osum[sl] = 0.f; osq[sl] = 0.f; }
-    }
     // ---- epilogue operands (defined here: the last chunk's iteration already requests them) -------------------------------
     const int nw = n0 + wave * WN;
     const bool vec_ok = FULL || ((p.N % 4 == 0) && (p.ldc % 4 == 0) && (((uintptr_t)p.C & 15) == 0));
     // An output unit (4 consecutive columns of one row) needs, besides its accumulators, values from memory: the bias, the
-    // fold vectors, the residual.  They are read in `load_ops`, used in `finish`.  The struct members are plain pointers (no
+    // LayerNorm vectors, the residual.  They are read in `load_ops`, used in `finish`.  The struct members are plain pointers (no
     // restrict), so hipcc must assume that a store to C changes them and keeps every load behind the store before it: emitted
     // unit by unit, each unit waits vmcnt(0) for its own loads AND for the acknowledgement of the store before -- one
     // dependent round trip to memory per unit (18 to 54 per lane).  The hot instantiations (PRE) therefore read the operands of
     // ALL units first (identical addresses -- the bias of a column group -- collapse into one load) and then only compute
     // and store.
-    struct ColOps { f32x4 bias, c4, g4, b4; };      // what depends on the column group only
+    struct ColOps { f32x4 bias, g4, b4; };          // what depends on the column group only
     // (not where it would spill: the 384-wide tile keeps 216 accumulators per lane; its QKV form fits, 475 VGPRs)
     constexpr bool RES = (EPI == EPI_BIAS_RES || EPI == EPI_BIAS_RES_LN);      // epilogues that add R[m][n]
     constexpr bool PRE = !(BN >= 384 && (EPI == EPI_BIAS || RES || EPI == EPI_EMBED));
     const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
     auto load_col = [&](int nb) __attribute__((always_inline)) {
-        ColOps o{zero4, zero4, zero4, zero4};
+        ColOps o{zero4, zero4, zero4};
         if (!FULL && nb >= p.N) return o;
         if constexpr (EPI == EPI_EMBED) {
             // no bias operand: it is part of the table rows (load_res)
@@ -432,19 +372,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
         } else if (p.bias) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) o.bias[q] = (nb + q < p.N) ? p.bias[nb + q] : 0.f;
-        }
-        if constexpr (LN_CONSUMER) {
-            if (p.ln_stats) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) o.c4[q] = (nb + q < p.N) ? p.ln_c[nb + q] : 0.f;
-            }
-        }
-        if constexpr (EPI == EPI_BIAS_RES && !FULL) {
-            if (p.r_stats) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (nb + q < p.N) { o.g4[q] = p.r_gamma[nb + q]; o.b4[q] = p.r_beta[nb + q]; }
-            }
         }
         if constexpr (EPI == EPI_BIAS_RES_LN) {      // FULL only: the affine part of the LayerNorm this epilogue applies
             o.g4 = *reinterpret_cast<const f32x4*>(p.ln_gamma + nb);
@@ -479,7 +406,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
         }
         return rr;
     };
-    auto finish = [&](int m, int nb, f32x4 a, int sl, const ColOps& o, f32x4 rr) __attribute__((always_inline)) {
+    auto finish = [&](int m, int nb, f32x4 a, const ColOps& o, f32x4 rr) __attribute__((always_inline)) {
         if (!FULL && (m >= p.M || nb >= p.N)) return;
         if constexpr (EPI == EPI_BIAS) {
             if (ksplit > 1) {      // raw partial tile; ld_partial is a multiple of 4 and covers N rounded up
@@ -488,36 +415,15 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
             }
         }
         f32x4 v;
-        bool folded = false;
-        if constexpr (LN_CONSUMER) {
-            if (p.ln_stats) {       // (acc - mu c_n) rstd + d_n ; d_n arrives as the bias
-                folded = true;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = (a[q] - amu[sl] * o.c4[q]) * ars[sl] + o.bias[q];
-            }
-        }
-        if (!folded) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = a[q] + o.bias[q];
-        }
+        for (int q = 0; q < 4; ++q) v[q] = a[q] + o.bias[q];
         if constexpr (EPI == EPI_BIAS_GELU) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] = gelu_erf(v[q]);
         }
         if constexpr (EPI == EPI_BIAS_RES) {
-            if constexpr (!FULL) {
-                if (p.r_stats) {        // the residual is LN(raw): normalise it on the fly
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) rr[q] = (rr[q] - rmu[sl]) * rrs[sl] * o.g4[q] + o.b4[q];
-                }
-            }
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] += rr[q];
-            if constexpr (LN_PRODUCER) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (FULL || nb + q < p.N) { osum[sl] += v[q]; osq[sl] += v[q] * v[q]; }
-            }
         }
         if constexpr (EPI == EPI_QKV) {
             if (nb < p.qcols) {      // qcols is a multiple of 4
@@ -540,7 +446,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
                 if (nb + q < p.N) cp[q] = v[q];
         }
     };
-    // every unit of this lane, in a fixed order with compile-time indices: fn(unit, column group, row, first column, accumulators, row slot)
+    // every unit of this lane, in a fixed order with compile-time indices: fn(unit, column group, row, first column, accumulators)
     constexpr int NUNIT = M32 ? 16 * NCB32 + NCB : NCB * NRB;
     constexpr int NCG = M32 ? 4 * NCB32 + NCB : NCB;
     auto for_units = [&](auto&& fn) __attribute__((always_inline)) {
@@ -554,16 +460,16 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
                     for (int qq = 0; qq < 4; ++qq) {
                         const f32x16& a = acc32[rb * NCB32 + cb];
                         fn((rb * NCB32 + cb) * 4 + qq, cb * 4 + qq, m0 + rb * 32 + li32, nw + cb * 32 + 8 * qq + 4 * lg32,
-                           f32x4{a[4 * qq], a[4 * qq + 1], a[4 * qq + 2], a[4 * qq + 3]}, rb);
+                           f32x4{a[4 * qq], a[4 * qq + 1], a[4 * qq + 2], a[4 * qq + 3]});
                     }
             // acc16[c][r] = C[m0 + 128 + li][nw + c*16 + 4*lg + r]
 #pragma unroll
-            for (int c = 0; c < NCB; ++c) fn(16 * NCB32 + c, 4 * NCB32 + c, m0 + 128 + li, nw + c * 16 + lg * 4, acc16[c], 4);
+            for (int c = 0; c < NCB; ++c) fn(16 * NCB32 + c, 4 * NCB32 + c, m0 + 128 + li, nw + c * 16 + lg * 4, acc16[c]);
         } else {
 #pragma unroll
             for (int c = 0; c < NCB; ++c)
 #pragma unroll
-                for (int r = 0; r < NRB; ++r) fn(c * NRB + r, c, m0 + r * 16 + li, nw + c * 16 + lg * 4, acc16[r * NCB + c], r);
+                for (int r = 0; r < NRB; ++r) fn(c * NRB + r, c, m0 + r * 16 + li, nw + c * 16 + lg * 4, acc16[r * NCB + c]);
         }
     };
     // EARLY: the operands are requested at the top of the LAST chunk's iteration and land under its MFMAs (2 us of them); the
@@ -586,14 +492,12 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
             for (int c = 0; c < NCB; ++c) col[c] = load_col(nw + c * 16 + lg * 4);
         }
         if constexpr (HAS_RES)
-            for_units([&](int i, int, int m, int nb, f32x4, int) __attribute__((always_inline)) { res[i] = load_res(m, nb); });
+            for_units([&](int i, int, int m, int nb, f32x4) __attribute__((always_inline)) { res[i] = load_res(m, nb); });
     };
-    // every wave issues exactly PIECES loads per chunk (the statistics loads above are younger: waiting for
-    // vmcnt <= PIECES still means chunk 0 has landed)
+    // every wave issues exactly PIECES loads per chunk: waiting for vmcnt <= PIECES means chunk 0 has landed
     if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if constexpr (VAR == 7) { ts_wall[1] = wall_clock64(); ts_cyc[0] = __builtin_readcyclecounter(); }
     read_frags(f0, 0, 0);
     constexpr int NG = READS;                       // one LDS read per scheduling group
     constexpr int MF = (MFMAS + NG - 1) / NG;       // MFMAs per group (the tail groups run dry, harmless)
@@ -602,31 +506,26 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     auto chunk = [&](int kc, auto last_tag) __attribute__((always_inline)) {
         constexpr bool LAST = decltype(last_tag)::value;
         const int buf = kc & 1;
-        if constexpr (VAR != 5) {
-            if constexpr (LAST && EARLY) request_ops();
-            read_frags(f1, buf, 1);
-            mma_half(f0);
-            SchedGroups<0, NG, MF, READS, 0, 0, CONV ? 6 : 0>::run();
+        if constexpr (LAST && EARLY) request_ops();
+        read_frags(f1, buf, 1);
+        mma_half(f0);
+        SchedGroups<0, NG, MF, READS, 0, 0, CONV ? 6 : 0>::run();
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (!LAST) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                         // chunk k+1 landed
+            __syncthreads();
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (!LAST) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                         // chunk k+1 landed
-                __syncthreads();
-                __builtin_amdgcn_sched_barrier(0);
-                // the last iterations re-fetch the last chunk (into a buffer nobody reads again) instead of being predicated:
-                // the body stays one basic block
-                const int kn = kbase + ((kc + 2 < nk) ? (kc + 2) * BK : (nk - 1) * BK);
-                dma(buf, kn);
-                read_frags(f0, buf ^ 1, 0);
-                mma_half(f1);
-                SchedGroups<0, NG, MF, READS, PIECES, 1, CONV ? 6 : 0>::run();
-            } else {
-                mma_half(f1);
-            }
-            __builtin_amdgcn_sched_barrier(0);
+            // the last iterations re-fetch the last chunk (into a buffer nobody reads again) instead of being predicated:
+            // the body stays one basic block
+            const int kn = kbase + ((kc + 2 < nk) ? (kc + 2) * BK : (nk - 1) * BK);
+            dma(buf, kn);
+            read_frags(f0, buf ^ 1, 0);
+            mma_half(f1);
+            SchedGroups<0, NG, MF, READS, PIECES, 1, CONV ? 6 : 0>::run();
         } else {
-            mma_half(f0);
-            mma_half(f0);
+            mma_half(f1);
         }
+        __builtin_amdgcn_sched_barrier(0);
     };
     if constexpr (PEEL) {
         for (int kc = 0; kc + 1 < nk; ++kc) chunk(kc, std::false_type{});
@@ -637,11 +536,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     // the re-fetched chunk of the second to last iteration must have landed before the workgroup gives its LDS back; with EARLY the
     // (younger) operand loads are waited for below, which covers it
     if constexpr (!EARLY) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (VAR == 7) { ts_wall[2] = wall_clock64(); ts_cyc[1] = __builtin_readcyclecounter(); }
-    if constexpr (VAR == 5 || VAR == 6) {
-        // diagnostics: skip the epilogue unless an impossible value appears (keeps the MFMAs live)
-        if (acc16[0][0] != 123456.789f) return;
-    }
 
     // ---- epilogue --------------------------------------------------------------------------------------------
     if constexpr (EPI == EPI_BIAS_RES_LN) {
@@ -851,65 +745,46 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
             }
         }
         // natural operand order: rows = output channels m, cols = tokens n; stored transposed into [B, C_total, 1, T]
-        // LN fold: the normalised operand is the token (column) side; a lane's columns are fixed per column block
-        constexpr int NCOL = M32 ? NCB32 + NCB : NCB;
-        float cmu[NCOL], crs[NCOL];
-        if (p.ln_stats) {
-#pragma unroll
-            for (int c = 0; c < NCOL; ++c) {
-                int n;
-                if constexpr (M32) n = (c < NCB32) ? nw + c * 32 + li32 : nw + (c - NCB32) * 16 + li;
-                else n = nw + c * 16 + li;
-                n = n < p.N ? n : p.N - 1;
-                row_mu_rstd(p.ln_stats, p.ln_parts, n, p.ln_dim, p.ln_eps, cmu[c], crs[c]);
-            }
-        }
-        // bias[m] / ln_c[m] of every row of this lane are read BEFORE the first store (see the note on `finish` below: behind a
-        // store to C the compiler must re-read them, one dependent round trip per value)
-        auto row_ops = [&](int m, float& bm, float& cm) __attribute__((always_inline)) {
-            const int mc = m < p.M ? m : p.M - 1;
-            bm = p.bias[mc];
-            cm = p.ln_stats ? p.ln_c[mc] : 0.f;
-        };
-        auto put = [&](int m, int n, float v, int cslot, float bm, float cm) __attribute__((always_inline)) {
+        // bias[m] of every row of this lane is read BEFORE the first store (see the note on `finish` above: behind a store to C
+        // the compiler must re-read it, one dependent round trip per value)
+        auto row_bias = [&](int m) __attribute__((always_inline)) { return p.bias[m < p.M ? m : p.M - 1]; };
+        auto put = [&](int m, int n, float v, float bm) __attribute__((always_inline)) {
             if (m >= p.M || n >= p.N) return;
             const int b = n / p.S, tok = n % p.S;
             if (tok == 0) return;
-            if (p.ln_stats) v = (v - cmu[cslot] * cm) * crs[cslot];
             p.C[((size_t)b * p.C_total + p.ch_off + m) * p.T + (tok - 1)] = v + bm;
         };
         if constexpr (M32) {
-            float bm32[4][16], cm32[4][16], bm16[4], cm16[4];
+            float bm32[4][16], bm16[4];
 #pragma unroll
             for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
-                for (int q = 0; q < 16; ++q) row_ops(m0 + rb * 32 + 8 * (q >> 2) + 4 * lg32 + (q & 3), bm32[rb][q], cm32[rb][q]);
+                for (int q = 0; q < 16; ++q) bm32[rb][q] = row_bias(m0 + rb * 32 + 8 * (q >> 2) + 4 * lg32 + (q & 3));
 #pragma unroll
-            for (int q = 0; q < 4; ++q) row_ops(m0 + 128 + lg * 4 + q, bm16[q], cm16[q]);
+            for (int q = 0; q < 4; ++q) bm16[q] = row_bias(m0 + 128 + lg * 4 + q);
 #pragma unroll
             for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
                 for (int cb = 0; cb < NCB32; ++cb)
 #pragma unroll
                     for (int q = 0; q < 16; ++q)
-                        put(m0 + rb * 32 + 8 * (q >> 2) + 4 * lg32 + (q & 3), nw + cb * 32 + li32, acc32[rb * NCB32 + cb][q], cb,
-                            bm32[rb][q], cm32[rb][q]);
+                        put(m0 + rb * 32 + 8 * (q >> 2) + 4 * lg32 + (q & 3), nw + cb * 32 + li32, acc32[rb * NCB32 + cb][q], bm32[rb][q]);
 #pragma unroll
             for (int c = 0; c < NCB; ++c)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) put(m0 + 128 + lg * 4 + q, nw + c * 16 + li, acc16[c][q], NCB32 + c, bm16[q], cm16[q]);
+                for (int q = 0; q < 4; ++q) put(m0 + 128 + lg * 4 + q, nw + c * 16 + li, acc16[c][q], bm16[q]);
         } else {
-            float bm[NRB][4], cm[NRB][4];
+            float bm[NRB][4];
 #pragma unroll
             for (int r = 0; r < NRB; ++r)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) row_ops(m0 + r * 16 + lg * 4 + q, bm[r][q], cm[r][q]);
+                for (int q = 0; q < 4; ++q) bm[r][q] = row_bias(m0 + r * 16 + lg * 4 + q);
 #pragma unroll
             for (int r = 0; r < NRB; ++r)
 #pragma unroll
                 for (int c = 0; c < NCB; ++c)
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) put(m0 + r * 16 + lg * 4 + q, nw + c * 16 + li, acc16[r * NCB + c][q], c, bm[r][q], cm[r][q]);
+                    for (int q = 0; q < 4; ++q) put(m0 + r * 16 + lg * 4 + q, nw + c * 16 + li, acc16[r * NCB + c][q], bm[r][q]);
         }
     } else {
         // swapped operand order: a lane holds C[m][nb .. nb+3].  FULL: the launcher proved M % 144 == 0,
@@ -918,50 +793,11 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
         if constexpr (PRE) {
             if constexpr (!EARLY) request_ops();
             if constexpr (HAS_RES)
-                for_units([&](int i, int cg, int m, int nb, f32x4 a, int sl) __attribute__((always_inline)) { finish(m, nb, a, sl, col[cg], res[i]); });
+                for_units([&](int i, int cg, int m, int nb, f32x4 a) __attribute__((always_inline)) { finish(m, nb, a, col[cg], res[i]); });
             else
-                for_units([&](int, int cg, int m, int nb, f32x4 a, int sl) __attribute__((always_inline)) { finish(m, nb, a, sl, col[cg], zero4); });
+                for_units([&](int, int cg, int m, int nb, f32x4 a) __attribute__((always_inline)) { finish(m, nb, a, col[cg], zero4); });
         } else {
-            for_units([&](int, int, int m, int nb, f32x4 a, int sl) __attribute__((always_inline)) { finish(m, nb, a, sl, load_col(nb), load_res(m, nb)); });
-        }
-        if constexpr (LN_PRODUCER) {
-            if (p.out_stats) {
-                // a row's columns of this tile live in the 4 lanes (li, lg = 0..3) of each of the 4 waves: two shuffles,
-                // then the waves meet in LDS (a zone past the staging buffers and the DMA landing zone)
-                float* part = lds_dummy + 512;                  // [4 waves][BM][2]
-#pragma unroll
-                for (int sl = 0; sl < NSLOT; ++sl) {
-                    float a = osum[sl], b = osq[sl];
-                    a += __shfl_xor(a, 16); b += __shfl_xor(b, 16);
-                    a += __shfl_xor(a, 32); b += __shfl_xor(b, 32);
-                    if (lg == 0) { part[(wave * BM + sl * 16 + li) * 2] = a; part[(wave * BM + sl * 16 + li) * 2 + 1] = b; }
-                }
-                __syncthreads();
-                if (tid < BM && m0 + tid < p.M) {
-                    float a = 0.f, b = 0.f;
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) { a += part[(w * BM + tid) * 2]; b += part[(w * BM + tid) * 2 + 1]; }
-                    // one slot per 64 columns whatever BN the launcher picked: this tile fills its first slot and
-                    // zeroes the others it covers
-                    float* o = p.out_stats + ((size_t)(m0 + tid) * p.out_parts + (n0 / 64)) * 2;
-                    o[0] = a; o[1] = b;
-#pragma unroll
-                    for (int k = 1; k < BN / 64; ++k)
-                        if (n0 / 64 + k < p.out_parts) { o[2 * k] = 0.f; o[2 * k + 1] = 0.f; }
-                }
-            }
-        }
-    }
-    if constexpr (VAR == 7) {
-        ts_wall[3] = wall_clock64();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // stores acknowledged
-        ts_wall[4] = wall_clock64();
-        if (tid == 0) {
-            unsigned long long* ts = reinterpret_cast<unsigned long long*>(const_cast<float*>(p.R)) + (size_t)blockIdx.x * 8;
-            for (int i = 0; i < 5; ++i) ts[i] = ts_wall[i];
-            ts[5] = ts_cyc[1] - ts_cyc[0];
-            ts[6] = __builtin_amdgcn_s_getreg((3 << 11) | 20);   // XCC_ID
-            ts[7] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
+            for_units([&](int, int, int m, int nb, f32x4 a) __attribute__((always_inline)) { finish(m, nb, a, load_col(nb), load_res(m, nb)); });
         }
     }
     } while (SK && sk_hi > sk_lo);
@@ -989,27 +825,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
         if (nb + q < N) cp[q] = acc[q] + (bias ? bias[nb + q] : 0.f);
 }
 
-// Diagnostic builds only (`ROHM_DIAG=1 python -m rohm_amd.build` defines ROHM_GEMM_DIAGNOSTICS): schedule variants
-// 5 / 6 / 7, forced tile widths and the occupancy / LDS-padding / target-workgroup knobs used by scripts/gemm_*.  The
-// shipped library has none of them: no environment lookups on the launch path, no diagnostic kernels in the binary.
-#ifdef ROHM_GEMM_DIAGNOSTICS
-static int gemm_variant() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("ROHM_GEMM_VARIANT");
-        v = e ? atoi(e) : 0;
-    }
-    return v;
-}
-static int diag_env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return (e && *e) ? atoi(e) : dflt;
-}
-#else
-static constexpr int gemm_variant() { return 0; }
-#endif
-
-template <int BN, int EPI, int VAR = 0, bool FULL = false, bool CONV = false>
+template <int BN, int EPI, bool FULL = false, bool CONV = false>
 static int launch_one(const GemmParams& p, hipStream_t s) {
     const int ksplit = (EPI == EPI_BIAS && p.ksplit > 1) ? p.ksplit : 1;
     int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * ksplit;
@@ -1018,31 +834,24 @@ static int launch_one(const GemmParams& p, hipStream_t s) {
     if (EPI == EPI_BIAS_RES_LN)      // row tiles dealt round-robin to the XCDs, rounded up to a multiple of 8 (the kernel's own map)
         tiles = (((p.M + BM - 1) / BM + kNumXCD - 1) / kNumXCD) * kNumXCD * ((p.N + BN - 1) / BN);
     if (EPI == EPI_OUT_T && p.sk_units > 0) {      // stream-K: one workgroup per CU, the units dealt out evenly
-        if (!(BN == 64 && !FULL && !CONV && VAR == 0)) { set_error("gemm: stream-K exists for the 144 x 64 output-head tiles only"); return ROHM_ERR_ARG; }
+        if (!(BN == 64 && !FULL && !CONV)) { set_error("gemm: stream-K exists for the 144 x 64 output-head tiles only"); return ROHM_ERR_ARG; }
         tiles = kSkWorkgroups;
     }
-#ifdef ROHM_GEMM_DIAGNOSTICS
-    static const int lds_pad = diag_env_int("ROHM_GEMM_LDS_PAD", 0);
-    static const bool occ2 = getenv("ROHM_GEMM_OCC2") != nullptr;      // allow two workgroups per CU
-#else
-    constexpr int lds_pad = 0;
-    constexpr bool occ2 = false;
-#endif
     // One workgroup per CU on purpose: with two co-resident workgroups the hardware hands BOTH freed slots of
     // a CU to the next tiles, so a 3-tiles-per-CU GEMM degenerates to 4 + 2 (measured 158 us vs 128 us); the
     // schedule already hides LDS / L2 latency without a partner wave.  Requesting more than half of the
     // 160 KiB LDS pins the residency to one.
-    size_t lds = (size_t)2 * (BM + BN) * BK * sizeof(float) + lds_pad;
+    size_t lds = (size_t)2 * (BM + BN) * BK * sizeof(float);
     lds += 2048;                           // landing zone of the dummy DMA pieces
     lds += 4 * BM * 2 * sizeof(float);     // row-stat exchange of the LayerNorm-producing epilogues
     const size_t lds_need = lds;
-    if (lds < 84 * 1024 && !occ2 && p.wg_per_cu < 2) lds = 84 * 1024;
+    if (lds < 84 * 1024 && p.wg_per_cu < 2) lds = 84 * 1024;
     static bool attr_set[64] = {};
     int dev = 0;
     ROHM_HIP_CHECK(hipGetDevice(&dev));
     if (dev < 64 && !attr_set[dev]) {
         const size_t lds_max = lds_need > 84 * 1024 ? lds_need : 84 * 1024;     // either residency of later launches
-        ROHM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_kernel<BN, EPI, VAR, FULL, CONV>),
+        ROHM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_kernel<BN, EPI, FULL, CONV>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
         attr_set[dev] = true;
     }
@@ -1058,7 +867,7 @@ static int launch_one(const GemmParams& p, hipStream_t s) {
     }
     {
     prof::Scope ps(label, 2.0 * p.M * p.N * p.K, 4.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N), s);
-    hipLaunchKernelGGL((gemm_f32_kernel<BN, EPI, VAR, FULL, CONV>), dim3(tiles), dim3(256), lds, s, p);
+    hipLaunchKernelGGL((gemm_f32_kernel<BN, EPI, FULL, CONV>), dim3(tiles), dim3(256), lds, s, p);
     ROHM_LAUNCH_CHECK();
     }
     if ((ksplit > 1 || (p.res_col0 > 0 && p.res_ksplit > 1)) && !p.ksplit_defer) {
@@ -1075,64 +884,35 @@ static int launch_one(const GemmParams& p, hipStream_t s) {
 
 static inline bool al16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
 
-template <int BN, int EPI, int VAR = 0>
+template <int BN, int EPI>
 static int launch_t(const GemmParams& p, hipStream_t s) {
     bool full = (p.M % BM == 0) && (p.N % BN == 0) && (p.ldc % 4 == 0) && al16(p.C) && al16(p.bias) && (p.bias || EPI == EPI_EMBED);
-    if (p.ln_stats || p.r_stats || p.out_stats) full = false;      // LayerNorm folding: general instantiation only
     if (EPI == EPI_BIAS_RES) full = full && (p.ldr % 4 == 0) && al16(p.R);
     if (EPI == EPI_EMBED) full = full && (p.ldtab % 4 == 0) && (p.ldtab0 % 4 == 0) && al16(p.tab) && al16(p.tab0);
     if (EPI == EPI_QKV) full = full && (p.qcols % 4 == 0);
-    full = full && al16(p.ln_c) && al16(p.r_gamma) && al16(p.r_beta);      // 16-byte loads of the LayerNorm vectors
-    if (EPI == EPI_OUT_T || (VAR != 0 && VAR != 7)) full = false;
+    if (EPI == EPI_OUT_T) full = false;
     if (p.conv_taps > 0) {
-        if constexpr (EPI == EPI_BIAS && VAR == 0 && BN <= 128) {
-            return full ? launch_one<BN, EPI, 0, true, true>(p, s) : launch_one<BN, EPI, 0, false, true>(p, s);
+        if constexpr (EPI == EPI_BIAS && BN <= 128) {
+            return full ? launch_one<BN, EPI, true, true>(p, s) : launch_one<BN, EPI, false, true>(p, s);
         } else {
             set_error("gemm: conv gather supports the bias epilogue and BN <= 128 only");
             return ROHM_ERR_UNSUPPORTED;
         }
     }
     if (full) {
-        if constexpr (EPI != EPI_OUT_T && (VAR == 0 || VAR == 7)) return launch_one<BN, EPI, VAR, true>(p, s);
+        if constexpr (EPI != EPI_OUT_T) return launch_one<BN, EPI, true>(p, s);
     }
-    return launch_one<BN, EPI, VAR, false>(p, s);
+    return launch_one<BN, EPI, false>(p, s);
 }
 
-// Workgroups a launch should at least produce before a wider tile is preferred: one per CU of the MI355X, or
-// fewer when the caller runs several independent launches side by side (ROHM_GEMM_TARGET_WGS).
-static int target_wgs() {
-#ifdef ROHM_GEMM_DIAGNOSTICS
-    static const int v = diag_env_int("ROHM_GEMM_TARGET_WGS", 256) > 0 ? diag_env_int("ROHM_GEMM_TARGET_WGS", 256) : 256;
-    return v;
-#else
-    return 256;
-#endif
-}
+// Workgroups a launch should at least produce before a wider tile is preferred: one per CU of the MI355X.
+constexpr int kTargetWgs = 256;
 
 template <int EPI>
 static int launch_bn(const GemmParams& p, hipStream_t s) {
     const int tm = (p.M + BM - 1) / BM;
     const int tiles128 = tm * ((p.N + 127) / 128);
-    const int want = target_wgs();
-#ifdef ROHM_GEMM_DIAGNOSTICS
-    const int var = gemm_variant();
-    const int force_bn = var / 10;            // 6x -> BN 64, 12x -> BN 128
-    if constexpr (EPI == EPI_BIAS) {
-        switch (var % 10) {                   // schedule variants exist for the plain epilogue only
-            case 5: return force_bn == 6 ? launch_t<64, EPI, 5>(p, s) : launch_t<128, EPI, 5>(p, s);
-            case 6: return force_bn == 6 ? launch_t<64, EPI, 6>(p, s) : launch_t<128, EPI, 6>(p, s);
-            case 7:                           // same tile choice as the shipped path
-                if (!p.R) break;
-                if (force_bn == 12) return launch_t<128, EPI, 7>(p, s);
-                if (p.N % 384 == 0 && tm * (p.N / 384) >= want) return launch_t<384, EPI, 7>(p, s);
-                if (p.N % 256 == 0 && tm * (p.N / 256) >= want) return launch_t<256, EPI, 7>(p, s);
-                return launch_t<128, EPI, 7>(p, s);
-            default: break;
-        }
-    }
-    if (force_bn == 6) return launch_t<64, EPI>(p, s);
-    if (force_bn == 12) return launch_t<128, EPI>(p, s);
-#endif
+    const int want = kTargetWgs;
     // Tile width: minimise  rounds x (BN + per-tile overhead),  rounds = ceil(tiles / workgroup slots).  Wider
     // tiles move fewer LDS-DMA bytes and fragment reads per MFMA and amortise the per-chunk barrier, but only while
     // every CU still gets a tile.  B = 64: N = 1536 -> 144x384, 1024 -> x256, 512 -> x128 (256 tiles each);
@@ -1143,7 +923,6 @@ static int launch_bn(const GemmParams& p, hipStream_t s) {
         const int cand[5] = {384, 256, 192, 128, 64};
         for (int bn : cand) {
             if (bn > 64 && p.N % bn != 0) continue;
-            if (p.out_stats && bn > 128) continue;      // the row-stat epilogue exists for the 16x16 layouts only
             const long tiles = (long)tm * ((p.N + bn - 1) / bn);
             const long cost = ((tiles + want - 1) / want) * (bn + 24);
             if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = bn; }
@@ -1168,7 +947,7 @@ static int launch_bn(const GemmParams& p, hipStream_t s) {
 // onto one XCD and never straddle a round of workgroups).
 static int ln_tile_width(int tm, int N) {
     auto ok = [&](int bn) { const int t = N / bn; return N % bn == 0 && t >= 1 && t <= 8 && 32 % t == 0; };
-    if (ok(128) && (long)tm * (N / 128) >= target_wgs()) return 128;
+    if (ok(128) && (long)tm * (N / 128) >= kTargetWgs) return 128;
     if (ok(64)) return 64;
     if (ok(128)) return 128;
     return 0;
@@ -1234,8 +1013,8 @@ static int launch_ln(const GemmParams& p, hipStream_t s) {
     ROHM_ARG_CHECK(p.ln_dim == p.N && p.ldc % 4 == 0 && p.ldr % 4 == 0 && al16(p.C) && al16(p.R) && al16(p.bias) && al16(p.ln_gamma) &&
                        al16(p.ln_beta) && (((uintptr_t)p.xln_stats) & 15) == 0 && p.ksplit <= 1 && p.conv_taps == 0,
                    "gemm: LayerNorm epilogue needs ln_dim == N and 16-byte aligned operands");
-    if (ln_tile_width(p.M / BM, p.N) == 128) return launch_one<128, EPI_BIAS_RES_LN, 0, true>(p, s);
-    return launch_one<64, EPI_BIAS_RES_LN, 0, true>(p, s);
+    if (ln_tile_width(p.M / BM, p.N) == 128) return launch_one<128, EPI_BIAS_RES_LN, true>(p, s);
+    return launch_one<64, EPI_BIAS_RES_LN, true>(p, s);
 }
 
 int launch_gemm(const GemmParams& p, int epi, hipStream_t s) {
@@ -1243,13 +1022,6 @@ int launch_gemm(const GemmParams& p, int epi, hipStream_t s) {
     ROHM_ARG_CHECK(p.lda % 4 == 0 && p.ldw % 4 == 0, "gemm: lda/ldw must be multiples of 4 floats");
     ROHM_ARG_CHECK(((uintptr_t)p.A % 16) == 0 && ((uintptr_t)p.W % 16) == 0, "gemm: A/W must be 16-byte aligned");
     ROHM_ARG_CHECK(p.M > 0 && p.N > 0, "gemm: empty problem");
-    if (p.out_stats) ROHM_ARG_CHECK(epi == EPI_BIAS_RES && p.out_parts == (p.N + 63) / 64 && p.out_parts <= 8 &&
-                                        p.out_parts % 2 == 0, "gemm: bad row-stat request");
-    ROHM_ARG_CHECK((!p.ln_stats || (p.ln_parts <= 8 && p.ln_parts % 2 == 0)) && (!p.r_stats || (p.r_parts <= 8 && p.r_parts % 2 == 0)),
-                   "gemm: LayerNorm folding supports 2..8 statistic slots (64 columns each)");
-    if (p.ln_stats) ROHM_ARG_CHECK((epi == EPI_QKV || epi == EPI_BIAS_GELU || epi == EPI_OUT_T) && p.ln_c && p.ln_dim > 0,
-                                   "gemm: LayerNorm folding needs ln_c / ln_dim and a supporting epilogue");
-    if (p.r_stats) ROHM_ARG_CHECK(epi == EPI_BIAS_RES && p.r_gamma && p.r_beta && p.ln_dim > 0, "gemm: bad residual LN");
     if (p.ksplit > 1) {
         ROHM_ARG_CHECK(epi == EPI_BIAS, "gemm: split-K supports the plain bias epilogue only");
         ROHM_ARG_CHECK(p.partial && p.ld_partial % 4 == 0 && p.ld_partial >= ((p.N + 3) / 4) * 4 &&

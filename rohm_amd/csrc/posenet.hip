@@ -30,9 +30,6 @@ constexpr float kF16WeightScale = 256.0f;      // fp16x3 mode: weight planes are
 
 struct LayerW {
     float *in_w, *in_b, *out_w, *out_b, *l1_w, *l1_b, *l2_w, *l2_b, *n1_w, *n1_b, *n2_w, *n2_b;
-    // LayerNorm folding (common.h GemmParams): with folding on, l1_w is gamma1-scaled, l1_b holds d, l1_c holds c;
-    // for layers >= 1 in_w is scaled by the PREVIOUS layer's gamma2, in_b holds d and in_c holds c.
-    float *in_c, *l1_c;
     // bf16 planes of the four weight matrices (precision ladder, planes.h); null in the exact-fp32 mode
     char *in_wp, *out_wp, *l1_wp, *l2_wp;
     // LayerNorm folded into the plane GEMMs (pp_fold): planes of gamma-scaled weights and the fold vectors (planes.h PlaneGemmParams)
@@ -57,19 +54,16 @@ struct rohm_posenet {
     float *t_w0T, *t_b0, *t_w2T, *t_b2;   // time MLP, weights stored [in][out]
     float* tok_table;  // [pe_len, D]  timestep token of every t (time MLP output + pe[0]), built once at create
     float *out_w, *out_b;                 // [Cout, D], [Cout]
-    float *out_c;                         // LayerNorm folding of the last norm2 into the output head
-    bool ln_fold;                         // LayerNorm folded into the CONSUMER GEMMs (opt-in, measured slower) or run as a kernel
     bool ln_fused;                        // LayerNorm inside the PRODUCER GEMMs (EPI_BIAS_RES_LN; default on, ROHM_POSENET_LN_FUSED=0: kernel)
     bool head_sk;                         // output head as a stream-K launch where the shape qualifies (default on, ROHM_POSENET_HEAD_SK=0: tiles)
     // The two launch forms above exchange data between workgroups of one launch (exchange.hip).  They are used only where the device
     // passed the layout guard at create (exch_allowed) and until an exchange failed on this handle (exch_fallback, set by
     // rohm_posenet_set_exchange: the Python loops then re-run the chunk on the exchange-free launches).
     bool chain_any;                       // chain at every batch size (tests: ROHM_POSENET_CHAIN_ANY=1)
-    bool stack_front;                     // stack: input embedding + layer 0's in-projection as leading phases (ROHM_POSENET_STACK_FRONT=0: own launches)
-    bool finish_pack;                     // sampling loop: DDPM update + the next step's pack as one kernel (ROHM_POSENET_FINISH_PACK=0: two)
     bool stack_tail;                      // sampling loop: output head + DDPM update + the next step's pack as the stack's closing phase -- ONE
-                                          // launch per denoising step (single-round launches: B = 64 / 32; ROHM_POSENET_STACK_TAIL=0: head and
-                                          // finish_pack as their own launches)
+                                          // launch per denoising step (ROHM_POSENET_STACK_TAIL=0: head and finish_pack as their own launches).
+                                          // Valid for any number of rounds of workgroups: a clip's tail reads only what its own workgroups
+                                          // wrote, and a tail launch never writes the pass counter (common.h StackParams::pass_add)
     int chain;                            // 0: one launch per GEMM; 1: the four GEMMs between two attention launches as ONE launch; 2 (default):
                                           // the whole encoder stack, attention included, as one launch (encoder_chain.hip; both need ln_fused;
                                           // ROHM_POSENET_CHAIN=0 | layer | stack)
@@ -282,7 +276,7 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(float* __restrict__ W, flo
 struct Workspace {
     float *apack, *h, *y, *qkv, *ctx, *ff, *tab0, *x0, *tok_all;
     char *hP, *yP, *ctxP, *ffP;   // planes of h / y / ctx / ff (split-bf16 mode; ctx and ff then exist as planes only)
-    float *stats_a, *stats_b;     // row (sum, sum of squares) partials of y / h: [M][D/64][2]
+    float *stats_a, *stats_b;     // row (sum, sum of squares) partials of y / h (plane modes): [M / 16][D / 16][16][2]
     float* xln;                   // scratch of the LayerNorm-producing GEMMs (common.h gemm_ln_*): status words, statistics
     float* sk;                    // scratch of the stream-K output head (common.h gemm_sk_*): flags, partial tiles
     float* econd;                 // [M, D] cond half of the input embedding + positional table + biases (sampling loop)
@@ -318,9 +312,9 @@ static Workspace carve(const rohm_posenet* p, int B, int T, float* base) {
     w.tab0 = take((size_t)B * p->D);
     w.x0 = take((size_t)B * p->Cin * T);
     w.tok_all = take((size_t)kLoopChunk * p->D);     // timestep tokens of one sample-loop call
-    // row statistics: one (sum, sum of squares) pair per 64 columns (fp32 LayerNorm folding) or per 16 columns (plane modes)
-    w.stats_a = take(M * (p->D / (p->nplane ? 16 : 64)) * 2);
-    w.stats_b = take(M * (p->D / (p->nplane ? 16 : 64)) * 2);
+    // row statistics of the plane modes' LayerNorm fold (pp_fold): one (sum, sum of squares) pair per 16 columns
+    w.stats_a = take(p->nplane ? M * (p->D / 16) * 2 : 0);
+    w.stats_b = take(p->nplane ? M * (p->D / 16) * 2 : 0);
     w.t_all = reinterpret_cast<int64_t*>(take(2 * (size_t)kLoopChunk));
     w.xln = take(gemm_ln_scratch_bytes((int)M, p->D) / sizeof(float));
     w.sk = take(gemm_sk_scratch_bytes() / sizeof(float));
@@ -360,9 +354,37 @@ struct TailArgs {
     int step;      // index of the step within the call: the launch's tags use pass counter + step
 };
 
-// Network body: from packed input (w.apack complete) to x0 channels [traj, Cin) in `x0_out`.  With `tail` (sampling loop) and a launch
-// plan that allows it -- the encoder stack with its leading phases, a single round of workgroups -- the stack launch also runs the
-// output head, the DDPM update and the next step's pack; `*tail_ran` says whether it did (x0_out is then NOT written: tail->x0 is).
+// The encoder's launch plan for B clips of S tokens on this handle, derived once per run_network call.
+struct EncoderPlan {
+    bool planes;       // split-bf16 GEMMs on planes (ROHM_GEMM_PRECISION): whole clips of 144 tokens, head dim 128
+    bool lnf;          // LayerNorm inside the producer GEMMs (EPI_BIAS_RES_LN): whole clips, widths whose column tiles pair up
+    bool chained;      // ... and the four GEMMs between two attention launches as ONE launch (encoder_chain.hip)
+    bool stacked;      // ... and the whole encoder, input embedding and attention included, as ONE launch from the packed input
+    bool tail;         // ... which, in the sampling loop, also closes the step: output head, DDPM update, the next step's pack
+};
+
+static EncoderPlan plan_encoder(const rohm_posenet* p, int B, int S) {
+    const int D = p->D, M = B * S;
+    EncoderPlan e{};
+    e.planes = p->nplane && S == 144 && D / p->H == 128;
+    e.lnf = p->ln_fused && !e.planes && gemm_ln_supported(M, D, D) && gemm_ln_supported(M, D, p->F);
+    // the chain needs the in-kernel LayerNorm exchange and the released widths; it runs from 32 clips on where whole rounds of its
+    // persistent workgroups fit the batch (encoder_chain_pays: 32, 48 .. 64, 122 .. 128, ...): elsewhere the launch-per-GEMM path
+    // picks a tile width per GEMM and keeps more CUs busy (ROHM_POSENET_CHAIN_ANY=1 chains every shape that has the form: tests).
+    // Tags: 4 l, 4 l + 1 (the chain's two LayerNorm exchanges and its flags); the head: 60.
+    e.chained = e.lnf && p->chain && encoder_chain_parts(M, D, p->F) != 0 && 4 * p->L + 2 <= 60 &&
+                ((B >= 32 && encoder_chain_pays(B)) || p->chain_any);
+    e.stacked = e.chained && p->chain == 2 && p->H == 4 && p->L <= 8 && S == 144 && D / p->H == 128;
+    // The tail phase of a clip reads only what the workgroups of that clip wrote in the same launch, so it is correct for any number
+    // of rounds of workgroups (B = 128 runs two: tests/test_gpu_chain.py); the launch never writes the pass counter (common.h
+    // StackParams::pass_add).
+    e.tail = e.stacked && p->stack_tail && D == 512 && p->Cout == 272;
+    return e;
+}
+
+// Network body: from packed input (w.apack complete) to x0 channels [traj, Cin) in `x0_out`.  With `tail` (sampling loop) and a plan
+// that allows it (EncoderPlan::tail) the stack launch also runs the output head, the DDPM update and the next step's pack;
+// `*tail_ran` says whether it did (x0_out is then NOT written: tail->x0 is).
 static int run_network(const rohm_posenet* p, const Workspace& w, const int64_t* t_dev, int64_t t_host,
                        const float* tok_pre, float* x0_out, int B, int T, hipStream_t s, bool cond_done = false,
                        const TailArgs* tail = nullptr, bool* tail_ran = nullptr) {
@@ -380,11 +402,7 @@ static int run_network(const rohm_posenet* p, const Workspace& w, const int64_t*
         }
     }
     int rc;
-    const bool planes = p->nplane && S == 144 && D / p->H == 128;
-    // the launch plan of the encoder (below): decided here because the stack also takes the input embedding and layer 0's in-projection
-    const bool lnf_plan = p->ln_fused && !(p->ln_fold && !planes) && !planes && gemm_ln_supported(M, D, D) && gemm_ln_supported(M, D, p->F);
-    const bool chained_plan = lnf_plan && p->chain && encoder_chain_parts(M, D, p->F) != 0 && 4 * p->L + 2 <= 60 && ((B >= 32 && encoder_chain_pays(B)) || p->chain_any);
-    const bool stacked_plan = chained_plan && p->chain == 2 && p->H == 4 && p->L <= 8 && S == 144 && D / p->H == 128;
+    const EncoderPlan plan = plan_encoder(p, B, S);
     GemmParams ge{};      // fused input embed (+cond embed, + biases, + positional table)
     ge.A = w.apack; ge.lda = p->KP; ge.W = p->w_embed; ge.ldw = p->KP; ge.C = w.h; ge.ldc = D;
     ge.M = M; ge.N = D; ge.K = p->KP; ge.S = S; ge.tab = p->tab; ge.tab0 = tok_pre ? tok_pre : w.tab0; ge.ldtab = D;
@@ -392,11 +410,10 @@ static int run_network(const rohm_posenet* p, const Workspace& w, const int64_t*
     if (cond_done) {      // w.econd = cond . Wc^T + bx + bc + pe[tok] already (embed_cond): contract x_t only and add it row by row
         ge.W = p->w_embed_x; ge.ldw = p->KX; ge.K = p->KX; ge.tab = w.econd; ge.tab_by_row = 1;
     }
-    const bool front = stacked_plan && p->stack_front;      // the embedding and layer 0's in-projection as the stack's leading phases
-    if (!front && (rc = launch_gemm(ge, EPI_EMBED, s))) return rc;
+    if (!plan.stacked && (rc = launch_gemm(ge, EPI_EMBED, s))) return rc;      // (the stack embeds in its leading phase)
     float* h = w.h;
     float* y = w.y;
-    if (planes) {
+    if (plan.planes) {
         // Split-bf16 mode: every producer hands its consumer bf16 planes (planes.h) -- LayerNorm writes fp32 (the residual)
         // AND planes, attention and the GELU GEMM write planes only; the embed output is cut by a small kernel (once per step).
         const int np = p->nplane;
@@ -442,47 +459,14 @@ static int run_network(const rohm_posenet* p, const Workspace& w, const int64_t*
         // the last norm2 has no GEMM of this kind behind it: one LayerNorm launch in front of the output head
         if (pf && (rc = launch_layernorm(h, p->layers[p->L - 1].n2_w, p->layers[p->L - 1].n2_b, M, D, s))) return rc;
     }
-    const bool fold = p->ln_fold && !planes;
-    // LayerNorm inside the producer GEMMs (out-projection, FF2): whole clips of 144 tokens, widths whose column tiles pair up
-    // (not while the stream records a hipGraph: the exchange's per-launch tag would be replayed -- the GEMM + LayerNorm pair then)
-    // (a stream that is recording a hipGraph keeps them: their tags come from the workspace's pass counter, a replay draws new ones)
-    const bool lnf = p->ln_fused && !fold && !planes && gemm_ln_supported(M, D, D) && gemm_ln_supported(M, D, p->F);
     // tag of exchanging launch number `idx` of this pass (2 l, 2 l + 1: the LayerNorm GEMMs of layer l; 60: the output head)
     auto tag_launch = [&](GemmParams& g, int idx) { g.xln_epoch = p->salt + (unsigned)idx; };
-    const int parts = D / 64;
-    auto ln_operand = [&](GemmParams& g, const float* stats, const float* c) {
-        g.ln_stats = stats; g.ln_parts = parts; g.ln_c = c; g.ln_dim = D; g.ln_eps = 1e-5f;
-    };
-    auto ln_residual = [&](GemmParams& g, const float* stats, const float* gamma, const float* beta) {
-        g.r_stats = stats; g.r_parts = parts; g.r_gamma = gamma; g.r_beta = beta; g.ln_dim = D; g.ln_eps = 1e-5f;
-    };
-    // The four GEMMs between two attention launches as ONE launch (encoder_chain.hip): needs the in-kernel LayerNorm exchange (lnf) and
-    // the released widths.  Layer l: [QKV of layer 0: its own launch] attention(l), chain(l) = out-proj + norm1, FF1, FF2 + norm2 and
-    // the QKV projection of layer l + 1.  Tags: 4 l, 4 l + 1 (the chain's two LayerNorm exchanges and its flags); the head: 60.
-    // From 32 clips on where whole rounds of its persistent workgroups fit the batch (encoder_chain_pays: 32, 48 .. 64, 122 .. 128, ...):
-    // elsewhere the launch-per-GEMM path picks a tile width per GEMM and keeps more CUs busy (ROHM_POSENET_CHAIN_ANY=1 chains every
-    // shape that has the form: tests).
-    const bool chained = lnf && p->chain && encoder_chain_parts(M, D, p->F) != 0 && 4 * p->L + 2 <= 60 && ((B >= 32 && encoder_chain_pays(B)) || p->chain_any);
-    const bool stacked = stacked_plan;
-    if (stacked != (chained && p->chain == 2 && p->H == 4 && p->L <= 8 && S == 144 && D / p->H == 128)) {
-        set_error("posenet: inconsistent launch plan");      // the two derivations of the plan must agree
-        return ROHM_ERR_ARG;
-    }
-    if (stacked) {
-        // ... and with attention inside, the layers looped in the kernel, the input embedding and layer 0's in-projection as leading
-        // phases: ONE launch from the packed input to the encoder's output
+    if (plan.stacked) {
+        // ONE launch from the packed input to the encoder's output: the input embedding and layer 0's in-projection as leading phases,
+        // then per layer attention and the four GEMMs, the layers looped in the kernel
         StackParams c{};
-        if (front) {
-            c.front = 1;
-            c.apack = ge.A; c.lda_pack = ge.lda; c.w_embed = ge.W; c.ldw_embed = ge.ldw; c.k_embed = ge.K;
-            c.S = S; c.tab = ge.tab; c.tab0 = ge.tab0; c.ldtab = ge.ldtab; c.ldtab0 = ge.ldtab0; c.tab_by_row = ge.tab_by_row;
-        } else {      // ROHM_POSENET_STACK_FRONT=0: the round-5 first form, embed and QKV of layer 0 as their own launches
-            const LayerW& l0 = p->layers[0];
-            GemmParams g{};
-            g.A = h; g.lda = D; g.W = l0.in_w; g.ldw = D; g.C = w.qkv; g.ldc = 3 * D; g.M = M; g.N = 3 * D; g.K = D;
-            g.bias = l0.in_b; g.qcols = D; g.qscale = qscale_of(p);
-            if ((rc = launch_gemm(g, EPI_QKV, s))) return rc;
-        }
+        c.apack = ge.A; c.lda_pack = ge.lda; c.w_embed = ge.W; c.ldw_embed = ge.ldw; c.k_embed = ge.K;
+        c.S = S; c.tab = ge.tab; c.tab0 = ge.tab0; c.ldtab = ge.ldtab; c.ldtab0 = ge.ldtab0; c.tab_by_row = ge.tab_by_row;
         c.h = h; c.y = y; c.ff = w.ff; c.qkv = w.qkv; c.ctx = w.ctx;
         c.M = M; c.D = D; c.F = p->F; c.L = p->L; c.n_head = p->H; c.qscale = qscale_of(p); c.ln_eps = 1e-5f;
         for (int l = 0; l < p->L; ++l) {
@@ -499,25 +483,25 @@ static int run_network(const rohm_posenet* p, const Workspace& w, const int64_t*
         c.flags = reinterpret_cast<unsigned long long*>(w.chain_flags);
         if (p->fault_left > 0) { --p->fault_left; c.fault = 1; }
         c.timeline = p->stack_timeline;
-        {
-            const int Gp = encoder_chain_parts(M, D, p->F), groups8 = (B + kNumXCD - 1) / kNumXCD * kNumXCD;
-            (void)Gp; (void)groups8;
-            if (tail && tail_ran && front && p->stack_tail && D == 512 && p->Cout == 272 && !fold) {
-                c.tail = 1;
-                c.t_out_w = p->out_w; c.t_out_b = p->out_b;
-                c.t_x = tail->x; c.t_cond = tail->cond; c.t_noise = tail->sigma == 0.f ? nullptr : tail->noise;
-                c.t_x0 = tail->x0; c.t_apack = tail->apack_next;
-                c.t_c1 = tail->c1; c.t_c2 = tail->c2; c.t_sigma = tail->sigma;
-                c.t_traj = p->traj; c.t_C = p->Cin; c.t_T = T; c.t_lda = p->KP; c.t_pass_ctr = tail->pass_ctr;
-                c.pass_add = (unsigned)tail->step;
-                *tail_ran = true;
-            }
+        if (tail && plan.tail) {
+            c.tail = 1;
+            c.t_out_w = p->out_w; c.t_out_b = p->out_b;
+            c.t_x = tail->x; c.t_cond = tail->cond; c.t_noise = tail->sigma == 0.f ? nullptr : tail->noise;
+            c.t_x0 = tail->x0; c.t_apack = tail->apack_next;
+            c.t_c1 = tail->c1; c.t_c2 = tail->c2; c.t_sigma = tail->sigma;
+            c.t_traj = p->traj; c.t_C = p->Cin; c.t_T = T; c.t_lda = p->KP; c.t_pass_ctr = tail->pass_ctr;
+            c.pass_add = (unsigned)tail->step;
         }
         if ((rc = launch_encoder_stack(c, s))) return rc;
-        if (c.tail) return ROHM_OK;      // the launch ended with x_prev in x (and the next step's pack): nothing left of the step
+        if (c.tail) {      // the launch ended with x_prev in x (and the next step's pack): nothing left of the step
+            if (tail_ran) *tail_ran = true;
+            return ROHM_OK;
+        }
     }
     const float qscale = qscale_of(p);
-    for (int l = 0; l < ((planes || !chained || stacked) ? 0 : p->L); ++l) {
+    // Layer l: [QKV of layer 0: its own launch] attention(l), chain(l) = out-proj + norm1, FF1, FF2 + norm2 and the QKV projection of
+    // layer l + 1.
+    for (int l = 0; l < ((plan.chained && !plan.stacked) ? p->L : 0); ++l) {
         const LayerW& lw = p->layers[l];
         if (l == 0) {
             GemmParams g{};
@@ -544,23 +528,18 @@ static int run_network(const rohm_posenet* p, const Workspace& w, const int64_t*
         if (p->fault_left > 0) { --p->fault_left; c.fault = 1; }
         if ((rc = launch_encoder_chain(c, s))) return rc;
     }
-    for (int l = 0; l < ((planes || chained) ? 0 : p->L); ++l) {
+    // one launch per GEMM (LayerNorm inside the producer GEMMs with lnf, else as its own kernel)
+    for (int l = 0; l < ((plan.planes || plan.chained) ? 0 : p->L); ++l) {
         const LayerW& lw = p->layers[l];
-        // With folding, h holds the RAW (pre-norm2) output of the previous layer for l >= 1 and stats_b its row sums.
         GemmParams g{};
         g.A = h; g.lda = D; g.W = lw.in_w; g.ldw = D; g.C = w.qkv; g.ldc = 3 * D; g.M = M; g.N = 3 * D; g.K = D;
         g.bias = lw.in_b; g.qcols = D; g.qscale = 1.0f / sqrtf((float)(D / p->H));
-        if (fold && l > 0) ln_operand(g, w.stats_b, lw.in_c);
         if ((rc = launch_gemm(g, EPI_QKV, s))) return rc;
         if ((rc = launch_attention(w.qkv, w.ctx, B, p->H, S, D / p->H, s))) return rc;
         g = GemmParams{};
         g.A = w.ctx; g.lda = D; g.W = lw.out_w; g.ldw = D; g.C = y; g.ldc = D; g.M = M; g.N = D; g.K = D;
         g.bias = lw.out_b; g.R = h; g.ldr = D;
-        if (fold) {
-            if (l > 0) ln_residual(g, w.stats_b, p->layers[l - 1].n2_w, p->layers[l - 1].n2_b);
-            g.out_stats = w.stats_a; g.out_parts = parts;
-        }
-        if (lnf) {      // y = norm1(h + out_proj(ctx)) in one launch
+        if (plan.lnf) {      // y = norm1(h + out_proj(ctx)) in one launch
             g.ln_gamma = lw.n1_w; g.ln_beta = lw.n1_b; g.ln_dim = D; g.ln_eps = 1e-5f;
             gemm_ln_bind(g, w.xln);
             tag_launch(g, 2 * l);
@@ -568,21 +547,16 @@ static int run_network(const rohm_posenet* p, const Workspace& w, const int64_t*
             if ((rc = launch_gemm(g, EPI_BIAS_RES_LN, s))) return rc;
         } else {
             if ((rc = launch_gemm(g, EPI_BIAS_RES, s))) return rc;
-            if (!fold && (rc = launch_layernorm(y, lw.n1_w, lw.n1_b, M, D, s))) return rc;
+            if ((rc = launch_layernorm(y, lw.n1_w, lw.n1_b, M, D, s))) return rc;
         }
         g = GemmParams{};
         g.A = y; g.lda = D; g.W = lw.l1_w; g.ldw = D; g.C = w.ff; g.ldc = p->F; g.M = M; g.N = p->F; g.K = D;
         g.bias = lw.l1_b;
-        if (fold) ln_operand(g, w.stats_a, lw.l1_c);
         if ((rc = launch_gemm(g, EPI_BIAS_GELU, s))) return rc;
         g = GemmParams{};
         g.A = w.ff; g.lda = p->F; g.W = lw.l2_w; g.ldw = p->F; g.C = h; g.ldc = D; g.M = M; g.N = D; g.K = p->F;
         g.bias = lw.l2_b; g.R = y; g.ldr = D;
-        if (fold) {
-            ln_residual(g, w.stats_a, lw.n1_w, lw.n1_b);
-            g.out_stats = w.stats_b; g.out_parts = parts;
-        }
-        if (lnf) {      // h = norm2(y + linear2(gelu(linear1(y))))
+        if (plan.lnf) {      // h = norm2(y + linear2(gelu(linear1(y))))
             g.ln_gamma = lw.n2_w; g.ln_beta = lw.n2_b; g.ln_dim = D; g.ln_eps = 1e-5f;
             gemm_ln_bind(g, w.xln);
             tag_launch(g, 2 * l + 1);
@@ -590,14 +564,13 @@ static int run_network(const rohm_posenet* p, const Workspace& w, const int64_t*
             if ((rc = launch_gemm(g, EPI_BIAS_RES_LN, s))) return rc;
         } else {
             if ((rc = launch_gemm(g, EPI_BIAS_RES, s))) return rc;
-            if (!fold && (rc = launch_layernorm(h, lw.n2_w, lw.n2_b, M, D, s))) return rc;
+            if ((rc = launch_layernorm(h, lw.n2_w, lw.n2_b, M, D, s))) return rc;
         }
     }
     {   // output head, transposed: rows = channels, cols = tokens
         GemmParams g{};
         g.A = p->out_w; g.lda = D; g.W = h; g.ldw = D; g.C = x0_out; g.M = p->Cout; g.N = M; g.K = D;
         g.bias = p->out_b; g.S = S; g.ch_off = p->Cin - p->Cout; g.C_total = p->Cin; g.T = T;
-        if (fold) ln_operand(g, w.stats_b, p->out_c);
         // B = 64: 2 x 144 tiles on 256 CUs -- dealt out as (tile, K chunk) units instead of a second, 1/8-full round (common.h sk_*)
         if (p->head_sk) { gemm_sk_bind(g, w.sk, reinterpret_cast<unsigned*>(w.xln)); tag_launch(g, 60); }
         if ((rc = launch_gemm(g, EPI_OUT_T, s))) return rc;
@@ -639,6 +612,45 @@ static int launch_finish_pack(const rohm_posenet* p, float* x0, const float* con
     return ROHM_OK;
 }
 
+// The create-time knobs, read in one place.  Each "off" form is a launch path that still runs where the default
+// cannot (small batches, the exchange fallback, forward calls) and that the tests use as a reference.
+//   ROHM_POSENET_LN_FUSED=0      LayerNorm as its own kernel instead of inside the producer GEMMs (EPI_BIAS_RES_LN)
+//   ROHM_POSENET_HEAD_SK=0       the output head as plain tiles instead of a stream-K launch
+//   ROHM_POSENET_CHAIN=0|layer|stack (default stack): one launch per GEMM / the four GEMMs of a layer / the whole encoder per launch
+//   ROHM_POSENET_CHAIN_ANY=1     chain / stack at every batch size that has the form (tests)
+//   ROHM_POSENET_STACK_TAIL=0    head, DDPM update and the next step's pack as their own launches behind the stack
+//   ROHM_POSENET_COND_HOIST=0    the full [x_t | cond] embedding every step instead of the cond half once per sampling call
+//   ROHM_GEMM_PRECISION=fp32|bf16x6|bf16x3|fp16x3 (default fp32): the precision ladder, split GEMMs on planes
+//   ROHM_PP_LNFOLD=0             plane modes: LayerNorm as its own kernel instead of folded into the plane GEMMs
+static int read_knobs(rohm_posenet* p) {
+    auto off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
+    p->ln_fused = !off("ROHM_POSENET_LN_FUSED");
+    p->head_sk = !off("ROHM_POSENET_HEAD_SK");
+    p->stack_tail = !off("ROHM_POSENET_STACK_TAIL");
+    p->cond_hoist = !off("ROHM_POSENET_COND_HOIST");
+    p->pp_fold = !off("ROHM_PP_LNFOLD");
+    const char* any = getenv("ROHM_POSENET_CHAIN_ANY");
+    p->chain_any = any && any[0] == '1';
+    const char* chain = getenv("ROHM_POSENET_CHAIN");
+    p->chain = 2;
+    if (chain && chain[0] == '0') p->chain = 0;
+    else if (chain && (!strcmp(chain, "layer") || !strcmp(chain, "1"))) p->chain = 1;
+    else if (chain && *chain && strcmp(chain, "stack") && strcmp(chain, "2")) {
+        set_error("posenet_create: ROHM_POSENET_CHAIN must be 0, layer or stack (got '%s')", chain);
+        return ROHM_ERR_ARG;
+    }
+    const char* prec = getenv("ROHM_GEMM_PRECISION");
+    p->nplane = 0;
+    if (prec && !strcmp(prec, "bf16x6")) p->nplane = 3;
+    else if (prec && !strcmp(prec, "bf16x3")) p->nplane = 2;
+    else if (prec && !strcmp(prec, "fp16x3")) p->nplane = kModeF16;
+    else if (prec && *prec && strcmp(prec, "fp32")) {
+        set_error("posenet_create: ROHM_GEMM_PRECISION must be fp32, bf16x6, bf16x3 or fp16x3 (got '%s')", prec);
+        return ROHM_ERR_ARG;
+    }
+    return ROHM_OK;
+}
+
 }  // namespace rohm
 
 using namespace rohm;
@@ -667,12 +679,12 @@ int rohm_posenet_create(rohm_posenet_t** out, const rohm_posenet_weights* w, int
     const size_t o_embed_x = cnt(D * p->KX);
     const size_t o_tok = cnt((size_t)w->pe_len * D);
     const size_t o_w0 = cnt(D * D), o_b0 = cnt(D), o_w2 = cnt(D * D), o_b2 = cnt(D);
-    const size_t o_ow = cnt((size_t)c_out * D), o_ob = cnt(c_out), o_oc = cnt(c_out);
+    const size_t o_ow = cnt((size_t)c_out * D), o_ob = cnt(c_out);
     const size_t o_tmp = cnt(D * D);                      // staging for transposes / embed build
     const size_t o_tmp2 = cnt(2 * D * (size_t)c_in + 2 * D);
     const size_t per_layer = align_up(3 * D * D, 64) + align_up(3 * D, 64) + align_up(D * D, 64) + align_up(D, 64) +
                              align_up(F * D, 64) + align_up(F, 64) + align_up(D * F, 64) + align_up(D, 64) +
-                             4 * align_up(D, 64) + align_up(3 * D, 64) + align_up(F, 64);
+                             4 * align_up(D, 64);
     const size_t o_layers = cnt(per_layer * n_layer);
     hipError_t e = hipMalloc(&p->arena, total * sizeof(float));
     if (e != hipSuccess) {
@@ -696,87 +708,39 @@ int rohm_posenet_create(rohm_posenet_t** out, const rohm_posenet_weights* w, int
     } while (0)
     p->w_embed = a + o_embed; p->w_embed_x = a + o_embed_x; p->tab = a + o_tab; p->pe = a + o_pe; p->tok_table = a + o_tok;
     p->t_w0T = a + o_w0; p->t_b0 = a + o_b0; p->t_w2T = a + o_w2; p->t_b2 = a + o_b2;
-    p->out_w = a + o_ow; p->out_b = a + o_ob; p->out_c = a + o_oc;
-    {
-        // LayerNorm folded into the surrounding GEMMs (no LN launches, no extra pass over the residual stream): built,
-        // parity-tested and MEASURED SLOWER than the separate 7.8 us kernel (B = 64: 19.38 vs 19.41 clips/s, B = 32:
-        // 16.38 vs 16.73, B = 8: 5.59 vs 5.86 -- the statistics exchange and the longer epilogues sit on every
-        // tile's critical path, the LN kernel overlaps nothing but costs little energy on a power-limited chip).
-        // Opt-in for further tuning: ROHM_POSENET_LNFOLD=1.
-        const char* e2 = getenv("ROHM_POSENET_LNFOLD");
-        p->ln_fold = (e2 && atoi(e2) == 1) && d_model <= 512;       // 8 statistic slots of 64 columns
-        // Round 4: LayerNorm inside the PRODUCER (out-projection / FF2) instead -- the column tiles of a row tile exchange their
-        // row statistics through L2 while they run and store LN(x) once (gemm_f32.hip EPI_BIAS_RES_LN): 16 launches and one
-        // write + read of the residual stream per layer less.  Default on; ROHM_POSENET_LN_FUSED=0 keeps the LayerNorm kernel.
-        const char* e6 = getenv("ROHM_POSENET_LN_FUSED");
-        p->ln_fused = !(e6 && e6[0] == '0');
-        const char* e7 = getenv("ROHM_POSENET_HEAD_SK");
-        p->head_sk = !(e7 && e7[0] == '0');
-        // Both launch forms assume a whole MI355X (256 CUs free for one launch, block b on XCD b % 8); the tags leave 6 bits for the
-        // launch index of a pass.  A device that does not look like that -- partitioned, CU-masked, shared -- gets the GEMM +
-        // LayerNorm kernel pair and plain output-head tiles from the start (exchange.hip: properties + environment + a probe launch).
-        const char* e9 = getenv("ROHM_POSENET_CHAIN");
-        p->chain = 2;
-        if (e9 && (e9[0] == '0')) p->chain = 0;
-        else if (e9 && (!strcmp(e9, "layer") || !strcmp(e9, "1"))) p->chain = 1;
-        else if (e9 && *e9 && strcmp(e9, "stack") && strcmp(e9, "2")) {
-            set_error("posenet_create: ROHM_POSENET_CHAIN must be 0, layer or stack (got '%s')", e9);
-            (void)hipFree(p->arena);
-            delete p;
-            return ROHM_ERR_ARG;
-        }
-        const char* e10 = getenv("ROHM_POSENET_CHAIN_ANY");
-        p->chain_any = e10 && e10[0] == '1';
-        const char* e11 = getenv("ROHM_POSENET_STACK_FRONT");
-        p->stack_front = !(e11 && e11[0] == '0');
-        const char* e12 = getenv("ROHM_POSENET_FINISH_PACK");
-        p->finish_pack = !(e12 && e12[0] == '0');
-        const char* e13 = getenv("ROHM_POSENET_STACK_TAIL");
-        p->stack_tail = !(e13 && e13[0] == '0');
-        p->ln_fused_env = p->ln_fused; p->head_sk_env = p->head_sk;
-        p->exch_fallback = false;
-        p->fault_left = 0;
-        p->stack_timeline = nullptr;
-        p->exch_reason = "not asked for";
-        p->exch_allowed = (p->ln_fused || p->head_sk) && 2 * n_layer + 1 <= 60 && exchange_layout_ok(device, &p->exch_reason);
-        if (!p->exch_allowed) p->ln_fused = p->head_sk = false;
-        {      // per-handle salt of the launch tags: a recycled workspace that holds another handle's (or anybody's) old words is stale
-            static std::atomic<unsigned> counter{0};
-            unsigned v = (unsigned)(uintptr_t)p ^ (unsigned)((uintptr_t)p >> 32) ^ ((counter.fetch_add(1u) + 1u) * 0x9e3779b9u);
-            v ^= v >> 16; v *= 0x7feb352du; v ^= v >> 15; v *= 0x846ca68bu; v ^= v >> 16;
-            p->salt = v & ~63u;
-        }
-        // The cond half of the input embedding (InputProcess of batch['cond'], model/posenet.py:85-87) does not change over a sampling
-        // loop: rohm_posenet_sample_loop computes it once per call and each step contracts the x_t half only (K 608 -> 320).
-        const char* e8 = getenv("ROHM_POSENET_COND_HOIST");
-        p->cond_hoist = !(e8 && e8[0] == '0');
-        // Opt-in precision ladder: ROHM_GEMM_PRECISION=bf16x6 | bf16x3 | fp16x3 runs the four Linears of every
-        // encoder layer as split-bf16 GEMMs on planes (gemm_pp.hip).  The default -- and every headline number -- is exact fp32.
-        const char* e3 = getenv("ROHM_GEMM_PRECISION");
-        p->nplane = 0;
-        if (e3 && !strcmp(e3, "bf16x6")) p->nplane = 3;
-        else if (e3 && !strcmp(e3, "bf16x3")) p->nplane = 2;
-        else if (e3 && !strcmp(e3, "fp16x3")) p->nplane = kModeF16;
-        else if (e3 && *e3 && strcmp(e3, "fp32")) {
-            set_error("posenet_create: ROHM_GEMM_PRECISION must be fp32, bf16x6, bf16x3 or fp16x3 (got '%s')", e3);
-            (void)hipFree(p->arena);
-            delete p;
-            return ROHM_ERR_ARG;
-        }
-        if (d_model / n_head != 128 || d_model % 64 || d_ff % 64) p->nplane = 0;   // shapes the plane kernels do not cover
-        // ... and the widths their LayerNorm / fold forms exist for: launch_layernorm_planes knows D = 256 / 512 / 1024, and with the
-        // fold the QKV GEMM's dynamic LDS request passes the 160 KiB of a CU from d_model = 1024 on.  Such a handle runs exact
-        // fp32 (rohm_posenet_precision reports 0) instead of failing on every forward.
-        if (p->nplane && d_model != 256 && d_model != 512) p->nplane = 0;
-        if (p->nplane) p->ln_fold = false;
-        p->wplanes = nullptr;
-        p->foldvec = nullptr;
-        p->wplanes_fold = nullptr;
-        // LayerNorm folded into the plane GEMMs (fifteen of the sixteen LayerNorm launches of a step disappear): two-plane modes
-        // only (the statistics tiles need the LDS a third plane occupies).  ROHM_PP_LNFOLD=0 switches it off.
-        const char* e5 = getenv("ROHM_PP_LNFOLD");
-        p->pp_fold = (p->nplane == 2 || p->nplane == kModeF16) && !(e5 && e5[0] == '0') && d_model % 128 == 0;
+    p->out_w = a + o_ow; p->out_b = a + o_ob;
+    if (int rc = read_knobs(p)) {
+        (void)hipFree(p->arena);
+        delete p;
+        return rc;
     }
+    p->ln_fused_env = p->ln_fused; p->head_sk_env = p->head_sk;
+    p->exch_fallback = false;
+    p->fault_left = 0;
+    p->stack_timeline = nullptr;
+    // Both exchanging launch forms assume a whole MI355X (256 CUs free for one launch, block b on XCD b % 8); the tags leave 6 bits
+    // for the launch index of a pass.  A device that does not look like that -- partitioned, CU-masked, shared -- gets the GEMM +
+    // LayerNorm kernel pair and plain output-head tiles from the start (exchange.hip: properties + environment + a probe launch).
+    p->exch_reason = "not asked for";
+    p->exch_allowed = (p->ln_fused || p->head_sk) && 2 * n_layer + 1 <= 60 && exchange_layout_ok(device, &p->exch_reason);
+    if (!p->exch_allowed) p->ln_fused = p->head_sk = false;
+    {      // per-handle salt of the launch tags: a recycled workspace that holds another handle's (or anybody's) old words is stale
+        static std::atomic<unsigned> counter{0};
+        unsigned v = (unsigned)(uintptr_t)p ^ (unsigned)((uintptr_t)p >> 32) ^ ((counter.fetch_add(1u) + 1u) * 0x9e3779b9u);
+        v ^= v >> 16; v *= 0x7feb352du; v ^= v >> 15; v *= 0x846ca68bu; v ^= v >> 16;
+        p->salt = v & ~63u;
+    }
+    if (d_model / n_head != 128 || d_model % 64 || d_ff % 64) p->nplane = 0;   // shapes the plane kernels do not cover
+    // ... and the widths their LayerNorm / fold forms exist for: launch_layernorm_planes knows D = 256 / 512 / 1024, and with the
+    // fold the QKV GEMM's dynamic LDS request passes the 160 KiB of a CU from d_model = 1024 on.  Such a handle runs exact
+    // fp32 (rohm_posenet_precision reports 0) instead of failing on every forward.
+    if (p->nplane && d_model != 256 && d_model != 512) p->nplane = 0;
+    p->wplanes = nullptr;
+    p->foldvec = nullptr;
+    p->wplanes_fold = nullptr;
+    // LayerNorm folded into the plane GEMMs (fifteen of the sixteen LayerNorm launches of a step disappear): two-plane modes
+    // only (the statistics tiles need the LDS a third plane occupies).
+    p->pp_fold = p->pp_fold && (p->nplane == 2 || p->nplane == kModeF16) && d_model % 128 == 0;
     float* tmp = a + o_tmp;
     float* tmp2 = a + o_tmp2;
     PUT(p->pe, w->pe, (size_t)w->pe_len * D);
@@ -812,7 +776,6 @@ int rohm_posenet_create(rohm_posenet_t** out, const rohm_posenet_weights* w, int
         d.in_w = take(3 * D * D); d.in_b = take(3 * D); d.out_w = take(D * D); d.out_b = take(D);
         d.l1_w = take(F * D); d.l1_b = take(F); d.l2_w = take(D * F); d.l2_b = take(D);
         d.n1_w = take(D); d.n1_b = take(D); d.n2_w = take(D); d.n2_b = take(D);
-        d.in_c = take(3 * D); d.l1_c = take(F);
         PUT(d.in_w, s.in_proj_w, 3 * D * D); PUT(d.in_b, s.in_proj_b, 3 * D);
         PUT(d.out_w, s.out_proj_w, D * D); PUT(d.out_b, s.out_proj_b, D);
         PUT(d.l1_w, s.lin1_w, F * D); PUT(d.l1_b, s.lin1_b, F);
@@ -894,21 +857,6 @@ int rohm_posenet_create(rohm_posenet_t** out, const rohm_posenet_weights* w, int
             delete p;
             return rc4 != ROHM_OK ? rc4 : ROHM_ERR_HIP;
         }
-    }
-    if (p->ln_fold) {
-        for (int l = 0; l < n_layer; ++l) {
-            LayerW& d = p->layers[l];
-            hipLaunchKernelGGL(ln_fold_kernel, dim3((unsigned)F), dim3(256), 0, 0, d.l1_w, d.l1_b, d.n1_w, d.n1_b, d.l1_c, (int)D);
-            if (l > 0) {
-                const LayerW& pr = p->layers[l - 1];
-                hipLaunchKernelGGL(ln_fold_kernel, dim3((unsigned)(3 * D)), dim3(256), 0, 0, d.in_w, d.in_b, pr.n2_w, pr.n2_b,
-                                   d.in_c, (int)D);
-            }
-        }
-        const LayerW& last = p->layers[n_layer - 1];
-        hipLaunchKernelGGL(ln_fold_kernel, dim3((unsigned)c_out), dim3(256), 0, 0, p->out_w, p->out_b, last.n2_w, last.n2_b,
-                           p->out_c, (int)D);
-        ROHM_HIP_CHECK(hipDeviceSynchronize());
     }
     *out = p;
     return ROHM_OK;
@@ -1055,17 +1003,17 @@ int rohm_posenet_sample_loop(const rohm_posenet_t* h, float* x, const float* con
         if (x_in_last && i == n_steps - 1)       // the reference keeps the input of the last step in batch['x_t']
             ROHM_HIP_CHECK(hipMemcpyAsync(x_in_last, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
         // x_t into the token-major pack: by its own kernel for the first step of the call, afterwards by the previous step's
-        // finish_pack (which also advanced the pass counter)
-        if ((i == 0 || !h->finish_pack) && (rc = launch_pack(h, x, w.apack, B, T, 0, s, pass_counter(w)))) return rc;
+        // finish_pack or stack tail
+        if (i == 0 && (rc = launch_pack(h, x, w.apack, B, T, 0, s, pass_counter(w)))) return rc;
         float* x0 = (x0_last && i == n_steps - 1) ? x0_last : w.x0;
         const float* nz = noise ? noise + (size_t)i * n : nullptr;
         // one launch per step where the plan allows (run_network decides): the stack closes with head + update + the next step's pack
         TailArgs tail{x, cond, nz, (x0_last && i == n_steps - 1) ? x0_last : nullptr, (i + 1 < n_steps) ? w.apack : nullptr,
                       c1, c2, sigma, pass_counter(w), i};
         bool tail_ran = false;
-        if ((rc = run_network(h, w, nullptr, t_model[i], nullptr, x0, B, T, s, hoist, h->finish_pack ? &tail : nullptr, &tail_ran))) return rc;
+        if ((rc = run_network(h, w, nullptr, t_model[i], nullptr, x0, B, T, s, hoist, &tail, &tail_ran))) return rc;
         if (tail_ran) continue;
-        if (i + 1 < n_steps && h->finish_pack) {
+        if (i + 1 < n_steps) {
             if ((rc = launch_finish_pack(h, x0, cond, x, nz, w.apack, c1, c2, sigma, B, T, pass_counter(w), s))) return rc;
         } else if ((rc = launch_finish(x0, cond, x, nz, x, c1, c2, sigma, h->traj, h->Cin, T, n, s))) {
             return rc;

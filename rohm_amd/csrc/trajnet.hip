@@ -34,18 +34,15 @@ __global__ __launch_bounds__(256) void pad_rows_kernel(const float* __restrict__
 // Timestep path of one step: SinusoidalPosEmb(32) -> Linear(32,128) -> Mish -> Linear(128,32)
 // (trajnet.py:120-125, heads.py:57-69), then every block's `Mish -> Linear(32, C_out)` (heads.py:34-38)
 // stacked into one [tb_total] vector.  One block per row (sample, or 1 when the batch shares t).
-__global__ __launch_bounds__(256) void time_path_kernel(const int64_t* __restrict__ t_dev, int64_t t_host,
-                                                        const int64_t* __restrict__ t_tab, const int* __restrict__ step_ctr,
-                                                        int tdim,
+__global__ __launch_bounds__(256) void time_path_kernel(const int64_t* __restrict__ t_dev, int64_t t_host, int tdim,
                                                         const float* __restrict__ w1T, const float* __restrict__ b1,
                                                         const float* __restrict__ w3T, const float* __restrict__ b3,
                                                         const float* __restrict__ tbwT, const float* __restrict__ tbb,
                                                         int tb_total, float* __restrict__ tb_all) {
     __shared__ float e[64], h[256], te[64];
     const int tid = threadIdx.x;
-    // t: per sample (t_dev), shared by the batch (t_host), or the entry of a device table selected by the step counter
-    // of a replayed hipGraph
-    const float tval = (float)(t_tab ? t_tab[*step_ctr] : (t_dev ? t_dev[blockIdx.x] : t_host));
+    // t: per sample (t_dev) or shared by the batch (t_host)
+    const float tval = (float)(t_dev ? t_dev[blockIdx.x] : t_host);
     const int half = tdim / 2;
     if (tid < tdim) {
         const int k = tid % half;
@@ -282,8 +279,7 @@ __global__ __launch_bounds__(256) void add_kernel(float* __restrict__ a, const f
 
 // The last three launches of a sampling-loop step as ONE: the head's Conv1d(32, c_traj, 1) (trajnet.py:158-161), the
 // ancestral update x_{t-1} = c1 x0 + c2 x_t + sigma noise (gaussian_diffusion_trajnet.py:440-466) and the zero-padded copy
-// of x_{t-1} that the next step's first convolution reads.  One thread per (row, channel); the per-step values are either
-// immediates or -- for the replayed hipGraph -- entries of device tables selected by the step counter.
+// of x_{t-1} that the next step's first convolution reads.  One thread per (row, channel).
 struct TailArgs {
     const float* fin; int ldfin;         // final block output [M, ldfin]
     const float* w; int ldw; int cin;    // head weight [c_traj, ldw] (cin <= 64 used columns), bias [c_traj]
@@ -291,24 +287,17 @@ struct TailArgs {
     float* x;                            // [M, c_traj]: x_t in, x_{t-1} out
     float* xin; int ldxin;               // padded copy [M, ldxin] (columns >= c_traj stay zero)
     float* x0_out;                       // nullable: the head's output itself
-    const float* noise;                  // immediates: this step's noise (nullable)
+    const float* noise;                  // this step's noise (nullable)
     float c1, c2, sigma;
-    const float* noise_base; const float* coef_tab; const int* step_ctr;   // tables (coef_tab != nullptr selects them)
     size_t M;
 };
 __global__ __launch_bounds__(256) void traj_tail_kernel(TailArgs a) {
     __shared__ float ws[32 * 65];
     for (int i = threadIdx.x; i < a.ctraj * a.cin; i += 256) ws[(i / a.cin) * 65 + i % a.cin] = a.w[(size_t)(i / a.cin) * a.ldw + i % a.cin];
     __syncthreads();
-    float c1 = a.c1, c2 = a.c2, sigma = a.sigma;
-    const float* noise = a.noise;
+    const float c1 = a.c1, c2 = a.c2, sigma = a.sigma;
+    const float* noise = sigma == 0.f ? nullptr : a.noise;
     const size_t n = a.M * a.ctraj;
-    if (a.coef_tab) {
-        const int k = *a.step_ctr;
-        c1 = a.coef_tab[3 * k]; c2 = a.coef_tab[3 * k + 1]; sigma = a.coef_tab[3 * k + 2];
-        noise = a.noise_base ? a.noise_base + (size_t)k * n : nullptr;
-    }
-    if (sigma == 0.f) noise = nullptr;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const size_t m = i / a.ctraj;
@@ -365,7 +354,6 @@ static inline size_t al(size_t n) { return (n + 63) / 64 * 64; }
 // caller's workspace; forward() publishes it here for the launch helpers of this host thread.
 constexpr size_t kSplitKFloats = (size_t)256 * 144 * 128;
 constexpr size_t kFuseMaxWork = (size_t)64 * 144 * 64;   // rows x channels of a level up to which the fused conv forms pay (B <= 64)
-constexpr int kGraphMaxSteps = 1024;       // steps per sample-loop call that the captured-graph path accepts
 static thread_local int tl_loop_mode = 0;             // form the last sample loop of this host thread ran in (rohm_trajnet_loop_mode)
 static thread_local float* tl_splitk = nullptr;       // partial slabs of the conv feeding the next kernel
 static thread_local float* tl_splitk_res = nullptr;   // partial slabs of a block's 1x1 residual conv (alive until its 2nd GroupNorm)
@@ -405,9 +393,8 @@ static void plan_split(GemmParams& g, float* buf = nullptr, SplitInfo* defer = n
 // Split plan of a fused [conv5 | 1x1 residual] launch (res_block): the residual columns' weights are zero outside the centre tap, so
 // their tiles walk K / 5 chunks and the workgroup slots they do not need go to the conv tiles as extra splits.  Returns false (plain
 // plan_split) where the two column ranges share tiles (cout % 64) or nothing is split anyway.
-static std::atomic<int> g_res_centre_tap{1};      // ROHM_TRAJ_RES_TAP=0 (read at create) keeps the uniform plan
 static bool plan_fused_residual(GemmParams& g, int co, float* buf, SplitInfo* defer, SplitInfo* defer_res) {
-    if (!g_res_centre_tap.load(std::memory_order_relaxed) || !buf || !defer || !defer_res || co % 64 != 0 || g.conv_taps != 5) return false;
+    if (!buf || !defer || !defer_res || co % 64 != 0 || g.conv_taps != 5) return false;
     const int tm = (g.M + 143) / 144, t = tm * (co / 64);            // conv tiles = residual tiles = t (144 x 64 tiles)
     const int slots = 256, nkr = g.conv_cin_pad / 32, nkc = g.K / 32, minc = g_split_min_chunks.load(std::memory_order_relaxed);
     if (2 * t > slots / 2) return false;
@@ -601,9 +588,7 @@ static TWs carve_t(const rohm_trajnet* h, int B, int T, float* base) {
         w.splitk_ctl = take(kSplitKFloats);
         w.splitk_res_ctl = take(kSplitKFloats);
     }
-    w.step_coef = take(3 * (size_t)kGraphMaxSteps);
-    w.step_t = reinterpret_cast<int64_t*>(take(2 * (size_t)kGraphMaxSteps));
-    w.step_ctr = reinterpret_cast<int*>(take(16));
+    w.step_t = reinterpret_cast<int64_t*>(take(2 * (size_t)kTbSteps));
     w.resident = take(resident_floats(B, T));
     w.floats = off;
     return w;
@@ -724,13 +709,11 @@ static int run_denoiser(const rohm_trajnet* h, const TWs& w, int B, int T, int l
 
 // head conv + DDPM update + padded copy of the new x (one launch, see traj_tail_kernel)
 static int run_tail(const rohm_trajnet* h, const TWs& w, float* x, float* x0_out, const float* noise, float c1, float c2,
-                    float sigma, const float* noise_base, const float* coef_tab, const int* step_ctr, size_t M,
-                    hipStream_t s) {
+                    float sigma, size_t M, hipStream_t s) {
     TailArgs a{};
     a.fin = w.fin; a.ldfin = kPadC; a.w = h->final_conv.w; a.ldw = h->final_conv.cin_pad; a.cin = h->final_conv.cin;
     a.bias = h->final_conv.b; a.ctraj = h->ctraj; a.x = x; a.xin = w.xin; a.ldxin = kPadC; a.x0_out = x0_out;
-    a.noise = noise; a.c1 = c1; a.c2 = c2; a.sigma = sigma; a.noise_base = noise_base; a.coef_tab = coef_tab;
-    a.step_ctr = step_ctr; a.M = M;
+    a.noise = noise; a.c1 = c1; a.c2 = c2; a.sigma = sigma; a.M = M;
     if (a.cin > 64 || a.cin % 4 != 0 || a.ctraj > 32) { set_error("trajnet: unsupported head shape"); return ROHM_ERR_UNSUPPORTED; }
     const size_t n = M * h->ctraj;
     size_t blocks = (n + 255) / 256;
@@ -741,11 +724,10 @@ static int run_tail(const rohm_trajnet* h, const TWs& w, float* x, float* x0_out
     return ROHM_OK;
 }
 
-static int run_time_path(const rohm_trajnet* h, const TWs& w, const int64_t* t_dev, int64_t t_host, int B,
-                         hipStream_t s, const int64_t* t_tab = nullptr, const int* step_ctr = nullptr) {
+static int run_time_path(const rohm_trajnet* h, const TWs& w, const int64_t* t_dev, int64_t t_host, int B, hipStream_t s) {
     const int rows = t_dev ? B : 1;
     prof::Scope ps("time_path", 0.0, 4.0 * h->tb_total * h->tdim, s);
-    hipLaunchKernelGGL(time_path_kernel, dim3(rows), dim3(256), 0, s, t_dev, t_host, t_tab, step_ctr, h->tdim, h->t_w1T, h->t_b1, h->t_w3T,
+    hipLaunchKernelGGL(time_path_kernel, dim3(rows), dim3(256), 0, s, t_dev, t_host, h->tdim, h->t_w1T, h->t_b1, h->t_w3T,
                        h->t_b3, h->tb_wT, h->tb_b, h->tb_total, w.tb_all);
     ROHM_LAUNCH_CHECK();
     return ROHM_OK;
@@ -755,9 +737,8 @@ static int run_time_path(const rohm_trajnet* h, const TWs& w, const int64_t* t_d
 int launch_time_path_steps(const rohm_trajnet* h, const TWs& w, const int64_t* t, int run, hipStream_t s) {
     ROHM_HIP_CHECK(hipMemcpyAsync(w.step_t, t, (size_t)run * sizeof(int64_t), hipMemcpyHostToDevice, s));
     prof::Scope ps("time_path", 0.0, 4.0 * h->tb_total * h->tdim * run, s);
-    hipLaunchKernelGGL(time_path_kernel, dim3(run), dim3(256), 0, s, w.step_t, (int64_t)0, (const int64_t*)nullptr,
-                       (const int*)nullptr, h->tdim, h->t_w1T, h->t_b1, h->t_w3T, h->t_b3, h->tb_wT, h->tb_b,
-                       h->tb_total, w.tb_steps);
+    hipLaunchKernelGGL(time_path_kernel, dim3(run), dim3(256), 0, s, w.step_t, (int64_t)0, h->tdim, h->t_w1T, h->t_b1, h->t_w3T,
+                       h->t_b3, h->tb_wT, h->tb_b, h->tb_total, w.tb_steps);
     ROHM_LAUNCH_CHECK();
     return ROHM_OK;
 }
@@ -801,75 +782,6 @@ static SideStream* side_stream(int device) {
     if (!ok) { (void)hipGetLastError(); (void)hipStreamDestroy(ss.s2); ss.s2 = nullptr; return nullptr; }
     ss.device = device;
     return &ss;
-}
-
-// Opt-in (ROHM_TRAJNET_GRAPH=1): measured on ROCm 7.2 / MI355X the replayed graph is SLOWER than plain stream launches
-// (100-step loop, B = 1: 96 ms vs 82 ms; B = 32: 106 vs 95; TrajControl B = 1: 152 vs 130) -- a graph kernel node costs
-// ~9.8 us against ~8.4 us for a stream launch, and the plain loop's host time only tracks the GPU because the queue
-// back-pressures.  The loop is bound by the GPU-side latency of ~98 small dependent kernels per step; fewer kernels
-// (fusion), not graphs, is what would help.
-static bool graph_replay_ok(int n_steps) {
-    const char* e = getenv("ROHM_TRAJNET_GRAPH");
-    return e && atoi(e) == 1 && !prof::enabled() && n_steps >= 3 && n_steps <= kGraphMaxSteps;
-}
-
-// Captured-graph sample loop (see rohm_trajnet_sample_loop).  Stream capture is not allowed on the legacy default
-// stream torch hands out by default, so the loop runs on a private non-blocking stream fenced with events against
-// the caller's stream.  Returns ROHM_ERR_UNSUPPORTED (nothing enqueued) if capture cannot start.
-static int sample_loop_graph(const rohm_trajnet* h, const TWs& w, float* x, const float* noise, const int64_t* t_model,
-                             const float* coef, float* x0_last, float* x_in_last, int n_steps, int B, int T, size_t M, size_t n,
-                             hipStream_t caller) {
-    static thread_local hipStream_t gs = nullptr;
-    static thread_local hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    if (!gs) {
-        if (hipStreamCreateWithFlags(&gs, hipStreamNonBlocking) != hipSuccess) { gs = nullptr; return ROHM_ERR_UNSUPPORTED; }
-        if (hipEventCreateWithFlags(&ev_in, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&ev_out, hipEventDisableTiming) != hipSuccess)
-            return ROHM_ERR_UNSUPPORTED;
-    }
-    ROHM_HIP_CHECK(hipEventRecord(ev_in, caller));
-    ROHM_HIP_CHECK(hipStreamWaitEvent(gs, ev_in, 0));
-    ROHM_HIP_CHECK(hipMemcpyAsync(w.step_coef, coef, (size_t)n_steps * 3 * sizeof(float), hipMemcpyHostToDevice, gs));
-    ROHM_HIP_CHECK(hipMemcpyAsync(w.step_t, t_model, (size_t)n_steps * sizeof(int64_t), hipMemcpyHostToDevice, gs));
-    ROHM_HIP_CHECK(hipMemsetAsync(w.step_ctr, 0, sizeof(int), gs));
-    auto one_step = [&](hipStream_t s) -> int {
-        int rc;
-        if ((rc = run_time_path(h, w, nullptr, 0, B, s, w.step_t, w.step_ctr))) return rc;
-        if ((rc = run_denoiser(h, w, B, T, 0, nullptr, s))) return rc;
-        if ((rc = run_tail(h, w, x, w.x0, nullptr, 0.f, 0.f, 0.f, noise, w.step_coef, w.step_ctr, M, s))) return rc;
-        return launch_advance_counter(w.step_ctr, s);
-    };
-    int rc = pad_rows(x, w.xin, M, h->ctraj, kPadC, gs);     // x_T; afterwards the tail kernel keeps the padded copy current
-    if (!rc && x_in_last && n_steps == 1)
-        ROHM_HIP_CHECK(hipMemcpyAsync(x_in_last, x, n * sizeof(float), hipMemcpyDeviceToDevice, gs));
-    if (!rc) rc = one_step(gs);                // step 0 directly (also sets every kernel's launch attributes)
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    bool captured = false;
-    if (!rc) {
-        if (hipStreamBeginCapture(gs, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const int rc_cap = one_step(gs);
-            const hipError_t e = hipStreamEndCapture(gs, &graph);
-            captured = !rc_cap && e == hipSuccess && graph &&
-                       hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
-        }
-        if (!captured) (void)hipGetLastError();        // plain launches on the private stream instead
-        for (int i = 1; i < n_steps && !rc; ++i) {
-            if (x_in_last && i == n_steps - 1 &&
-                hipMemcpyAsync(x_in_last, x, n * sizeof(float), hipMemcpyDeviceToDevice, gs) != hipSuccess) { rc = ROHM_ERR_HIP; break; }
-            if (captured) rc = (hipGraphLaunch(exec, gs) == hipSuccess) ? ROHM_OK : ROHM_ERR_HIP;
-            else rc = one_step(gs);
-        }
-    }
-    if (!rc && x0_last)
-        ROHM_HIP_CHECK(hipMemcpyAsync(x0_last, w.x0, n * sizeof(float), hipMemcpyDeviceToDevice, gs));
-    (void)hipEventRecord(ev_out, gs);
-    (void)hipStreamWaitEvent(caller, ev_out, 0);
-    (void)hipStreamSynchronize(gs);            // the graph objects must outlive their launches
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    if (rc == ROHM_ERR_HIP) set_error("trajnet_sample_loop: hipGraph launch failed");
-    return rc;
 }
 
 }  // namespace rohm
@@ -1157,7 +1069,6 @@ int rohm_trajnet_forward(const rohm_trajnet_t* h, const float* x_t, const float*
     }
     tl_splitk = w.splitk;
     tl_splitk_res = w.splitk_res;
-    { const char* e = getenv("ROHM_TRAJ_RES_TAP"); g_res_centre_tap.store(!(e && e[0] == '0'), std::memory_order_relaxed); }
     const size_t M = (size_t)B * T;
     if ((rc = pad_rows(x_t, w.xin, M, h->ctraj, kPadC, s))) return rc;
     if ((rc = pad_rows(cond, w.cin, M, h->ctraj, kPadC, s))) return rc;
@@ -1193,7 +1104,6 @@ int rohm_trajnet_sample_loop(const rohm_trajnet_t* h, float* x, const float* con
     tl_splitk = w.splitk;
     tl_splitk_res = w.splitk_res;
     tl_loop_mode = 0;
-    { const char* e = getenv("ROHM_TRAJ_RES_TAP"); g_res_centre_tap.store(!(e && e[0] == '0'), std::memory_order_relaxed); }
     const size_t M = (size_t)B * T, n = M * h->ctraj;
     // cond / control_cond do not change over the loop: pad them and run the (time-free) cond encoder once
     if ((rc = pad_rows(cond, w.cin, M, h->ctraj, kPadC, s))) return rc;
@@ -1204,15 +1114,6 @@ int rohm_trajnet_sample_loop(const rohm_trajnet_t* h, float* x, const float* con
     if ((rc = run_cond_encoder(h, w, B, T, s))) return rc;
     for (int i = 0; i < n_steps; ++i)
         ROHM_ARG_CHECK(coef[3 * i + 2] == 0.f || noise, "trajnet_sample_loop: noise is required when sigma != 0");
-    if (graph_replay_ok(n_steps)) {
-        // hipGraph replay (opt-in, see graph_replay_ok): one denoising step is captured into a hipGraph whose kernels read
-        // the per-step values (timestep, c1 / c2 / sigma, noise slice) from device tables through a device-side step
-        // counter, and the graph is replayed for the remaining steps.
-        rc = sample_loop_graph(h, w, x, noise, t_model, coef, x0_last, x_in_last, n_steps, B, T, M, n, s);
-        if (rc == ROHM_OK) tl_loop_mode = 2;
-        if (rc != ROHM_ERR_UNSUPPORTED) return rc;
-        // capture not available on this stream / runtime: fall through to the plain loop
-    }
     if ((rc = pad_rows(x, w.xin, M, h->ctraj, kPadC, s))) return rc;     // x_T; the tail kernel keeps the padded copy current
     bool control_pre_done = false;
     if (resident_ok(h, B, T, n_steps, s)) {
@@ -1267,7 +1168,7 @@ int rohm_trajnet_sample_loop(const rohm_trajnet_t* h, float* x, const float* con
         }
         // head conv + ancestral update + padded copy for the next step: one launch (three before)
         if ((rc = run_tail(h, w, x, (x0_last && i == n_steps - 1) ? x0_last : nullptr, noise ? noise + (size_t)i * n : nullptr,
-                           c1, c2, sigma, nullptr, nullptr, nullptr, M, s)))
+                           c1, c2, sigma, M, s)))
             return fail(rc);
     }
     return ROHM_OK;
