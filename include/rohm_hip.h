@@ -465,6 +465,23 @@ int rohm_amass_metrics(const float* joints_clean, const float* joints_rec, const
                        unsigned occ_joint_mask, int occ_start, int occ_end, int B, int T, double* out,
                        rohm_stream_t stream);
 
+/* PROX / EgoBody evaluation metrics (eval_prox_egobody.py:172-270) as per-clip partial sums, one workgroup per clip.
+ * joints_rec [B,T,22,3] in canonical coordinates; each clip is mapped back to scene coordinates with
+ * inv(trans_scene2cano[b]) ([B,4,4], a general matrix inverted in float64, rounded to float32, then applied as
+ * points_coord_trans, utils/other_utils.py:139-143).  ground_height [B] (floats: a batch may mix recordings);
+ * up_axis 2 = PROX (z up, horizontal x/y), 1 = EgoBody (y up, horizontal x/z).  joints_gt [B,T_gt,22,3] (scene
+ * coordinates, first T frames used, T_gt >= T) and mask_vis [B,T,22] (1 = visible; only with joints_gt) may be NULL.
+ * joints_scene [B,T,22,3] receives the back-transformed joints when non-NULL.  3 <= T <= 800.  out [B,11] doubles:
+ *   0 skating frames (of T-1)             1 sum |acc_rec| (of (T-2)*22)     2 sum |acc_rec - acc_gt| (of (T-2)*22)
+ *   3 toe entries with d < -0.05 (of 2T)  4 sum min(d, 0) over toes (of 2T)  5 sum global error (of 22T)
+ *   6 sum local (root-relative) error (of 22T)   7 sum local*mask   8 sum mask   9 sum local*(1-mask)   10 sum (1-mask)
+ * with d = toe height - ground_height; 2 and 5-10 are 0 without joints_gt, 7-10 without mask_vis.  The script's
+ * numbers are sums over clips divided by the counts in brackets (vis / occ: 7 / 8 and 9 / 10).  No allocation, no
+ * synchronisation. */
+int rohm_scene_metrics(const float* joints_rec, const float* trans_scene2cano, const float* ground_height, int up_axis,
+                       const float* joints_gt, int T_gt, const float* mask_vis, float* joints_scene, int B, int T,
+                       double* out, rohm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
