@@ -38,6 +38,11 @@ __device__ __forceinline__ void at_dma16(const float* src, float* lds_dst) {
 #define AT_STAMP(i)
 #endif
 
+// Q fragments of one work item: lane (query li, g) holds Q[q][16 ks + 4 g + j], j = 0..3 -- qf of the owned blocks, qc of the
+// cooperative one
+template <int NPASS>
+struct AtQFrags { f32x4 f[NPASS][8]; f32x4 c[8]; };
+
 // NPO = 0: ctx is the fp32 matrix [n_seq * 144][n_head * 128]; NPO = 2 / 3 / 16: ctx receives the bf16 (fp16) PLANES of that matrix
 // instead (planes.h; the consumer is the out-projection of the split-bf16 path, gemm_pp.hip).  For plane output the P.V
 // MFMAs run with their operands exchanged (O^T = V^T P^T: the same products summed in the same order), which leaves a lane
@@ -45,9 +50,12 @@ __device__ __forceinline__ void at_dma16(const float* src, float* lds_dst) {
 // One work item = query blocks [q0, q0 + nq) of (clip, head) `item`, computed by the NW waves of the calling workgroup: every wave
 // OWNS NPASS query blocks (q0 + ps * NW + wave), a last block beyond NW * NPASS is computed cooperatively.  NPASS = 2 (NW = 4: a whole
 // item on four waves, encoder_chain.hip at 4 workgroups per clip): all QK^T first, then the softmaxes, then all P.V.
-template <int NW, int NPO = 0, int AUX = 0, int NPASS = 1>
+// RESIDENT: the operands are in place already (encoder_chain.hip's head-aligned in-projection wrote them): all of K in the K image,
+// all of V in the V image -- stored with K's XOR swizzle, so that the epilogue's column-owned writes are conflict-free -- and the Q
+// fragments in `qin`.  No DMA is issued, no vmcnt is waited on, qkv is not read.
+template <int NW, int NPO = 0, int AUX = 0, int NPASS = 1, bool RESIDENT = false>
 __device__ __forceinline__ void attention_item(const float* __restrict__ qkv, float* __restrict__ ctx, int n_head, int item, int q0,
-                                               int nq, float* smem, const int tid AT_TL_PARAM) {
+                                               int nq, float* smem, const int tid AT_TL_PARAM, const AtQFrags<NPASS>* qin = nullptr) {
     constexpr int OWNED = NW * NPASS;               // query blocks owned by one wave each
     constexpr int NQP = (NPASS == 2) ? 72 / NW : ((NW == 8) ? 9 : 10);      // Q staging pieces (1 KiB) per wave
     constexpr int NKP = 24 / NW;                    // K pieces per wave per 48-key group
@@ -71,19 +79,15 @@ __device__ __forceinline__ void attention_item(const float* __restrict__ qkv, fl
     const float* qg = qkv + (size_t)seq * AT_S * ldq + head * AT_DH;
     const float* kg = qg + D;
     const float* vg = qg + 2 * D;
+    // V[key][64 db + 4 li .. + 3] in the V image (RESIDENT: XOR-swizzled like K)
+    auto vaddr = [&](int key, int db) __attribute__((always_inline)) {
+        if constexpr (RESIDENT) return Vs + key * AT_DH + (((db * 16 + li) ^ (key & 15)) << 2);
+        else return Vs + key * AT_DH + db * 64 + li * 4;
+    };
 
     // ---- issue: Q rows of this workgroup -> V buffer (swizzled like K), all of K -> K buffer ------------------
     const int half_row = lane >> 5, cphys = lane & 31;
-#pragma unroll
-    for (int i = 0; i < NQP; ++i) {
-        const int lp = i * NW + wave;                                   // local piece = local rows 2lp, 2lp + 1
-        const bool ok = lp < nq * 8;
-        const int lr = ok ? 2 * lp + half_row : half_row;
-        const float* src = qg + (size_t)(q0 * 16 + lr) * ldq + ((cphys ^ (lr & 15)) << 2);
-        at_dma16<AUX>(src, ok ? Vs + lp * 256 : dummy);
-    }
-    // Only what the first MFMA needs goes out first (Q + the first 48 keys): with the rest of K and V queued behind
-    // them every CU's first bytes arrive later (measured: first MFMA at 7.2 us instead of ~5 at B = 64).
+    f32x4 qf[NPASS][8], qc[8];
     auto issue_k = [&](int G) {
 #pragma unroll
         for (int i = 0; i < NKP; ++i) {
@@ -92,25 +96,6 @@ __device__ __forceinline__ void attention_item(const float* __restrict__ qkv, fl
             at_dma16<AUX>(kg + (size_t)row * ldq + ((cphys ^ (row & 15)) << 2), Ks + piece * 256);
         }
     };
-    issue_k(0);
-    AT_WAIT_VM(NKP);                     // this wave's Q pieces have landed
-    __builtin_amdgcn_s_barrier();        // ... and everybody else's
-    AT_STAMP(1);
-
-    // Q fragments: lane (query li, g) holds Q[q][16 ks + 4 g + j], j = 0..3
-    f32x4 qf[NPASS][8], qc[8];
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-#pragma unroll
-        for (int ps = 0; ps < NPASS; ++ps)
-            qf[ps][ks] = *reinterpret_cast<const f32x4*>(Vs + ((ps * NW + wave) * 16 + li) * AT_DH + (((ks * 4 + lg) ^ li) << 2));
-        qc[ks] = *reinterpret_cast<const f32x4*>(Vs + ((coop ? OWNED : 0) * 16 + li) * AT_DH + (((ks * 4 + lg) ^ li) << 2));
-    }
-    AT_WAIT_LGKM0();
-    __builtin_amdgcn_s_barrier();        // every wave has its Q: the V buffer may be overwritten
-    // The rest of K and V is issued in three instalments, one ahead of each QK^T group: issuing all 27 (54) DMA
-    // instructions here stalls every wave in the issue loop until the CU's memory queue has drained (measured: first
-    // MFMA at 16k cycles although Q had landed at 8k).
     auto issue_v = [&](int part) {
 #pragma unroll
         for (int i = part * NV3; i < (part + 1) * NV3; ++i) {
@@ -118,12 +103,49 @@ __device__ __forceinline__ void attention_item(const float* __restrict__ qkv, fl
             at_dma16<AUX>(vg + (size_t)(2 * piece + half_row) * ldq + (cphys << 2), Vs + piece * 256);
         }
     };
-    // Issue order behind Q and the first key group: K1, K2 | V0, V1 | V2 -- all of K ahead of all of V.  Measured against the
-    // round-2 order K1, V0 | K2, V1 | V2 (profiles/r5_a_attn_split_timeline.txt): the kernel is not gated by the arrival of the
-    // later key groups in either order (their stamps follow the previous group's 96 MFMAs), the K-first order is 0.7 % (B = 32) /
-    // 1.5 % (B = 64) faster.
-    issue_k(1);
-    issue_k(2);
+    if constexpr (RESIDENT) {
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+#pragma unroll
+            for (int ps = 0; ps < NPASS; ++ps) qf[ps][ks] = qin->f[ps][ks];
+            qc[ks] = qin->c[ks];
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < NQP; ++i) {
+            const int lp = i * NW + wave;                                   // local piece = local rows 2lp, 2lp + 1
+            const bool ok = lp < nq * 8;
+            const int lr = ok ? 2 * lp + half_row : half_row;
+            const float* src = qg + (size_t)(q0 * 16 + lr) * ldq + ((cphys ^ (lr & 15)) << 2);
+            at_dma16<AUX>(src, ok ? Vs + lp * 256 : dummy);
+        }
+        // Only what the first MFMA needs goes out first (Q + the first 48 keys): with the rest of K and V queued behind
+        // them every CU's first bytes arrive later (measured: first MFMA at 7.2 us instead of ~5 at B = 64).
+        issue_k(0);
+        AT_WAIT_VM(NKP);                     // this wave's Q pieces have landed
+        __builtin_amdgcn_s_barrier();        // ... and everybody else's
+        AT_STAMP(1);
+
+        // Q fragments: lane (query li, g) holds Q[q][16 ks + 4 g + j], j = 0..3
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+#pragma unroll
+            for (int ps = 0; ps < NPASS; ++ps)
+                qf[ps][ks] = *reinterpret_cast<const f32x4*>(Vs + ((ps * NW + wave) * 16 + li) * AT_DH + (((ks * 4 + lg) ^ li) << 2));
+            qc[ks] = *reinterpret_cast<const f32x4*>(Vs + ((coop ? OWNED : 0) * 16 + li) * AT_DH + (((ks * 4 + lg) ^ li) << 2));
+        }
+        AT_WAIT_LGKM0();
+        __builtin_amdgcn_s_barrier();        // every wave has its Q: the V buffer may be overwritten
+        // The rest of K and V is issued in three instalments, one ahead of each QK^T group (issue_v): issuing all 27 (54) DMA
+        // instructions here stalls every wave in the issue loop until the CU's memory queue has drained (measured: first
+        // MFMA at 16k cycles although Q had landed at 8k).
+        // Issue order behind Q and the first key group: K1, K2 | V0, V1 | V2 -- all of K ahead of all of V.  Measured against the
+        // round-2 order K1, V0 | K2, V1 | V2 (profiles/r5_a_attn_split_timeline.txt): the kernel is not gated by the arrival of the
+        // later key groups in either order (their stamps follow the previous group's 96 MFMAs), the K-first order is 0.7 % (B = 32) /
+        // 1.5 % (B = 64) faster.
+        issue_k(1);
+        issue_k(2);
+    }
 
     // ---- QK^T of the owned block, one 48-key group at a time as K lands ----------------------------------------
     f32x4 sacc[NPASS][AT_NB];
@@ -134,17 +156,19 @@ __device__ __forceinline__ void attention_item(const float* __restrict__ qkv, fl
 #pragma unroll
     for (int G = 0; G < 3; ++G) {
         // (vmcnt retires in issue order)  issue order: Q, K0 | K1, K2 | V0, V1 | V2
-        if (G == 0) {
-            AT_WAIT_VM(2 * NKP);                     // K0 landed; K1, K2 may be in flight
-        } else if (G == 1) {
-            issue_v(0);
-            issue_v(1);
-            AT_WAIT_VM(NKP + 2 * NV3);               // K1 landed; K2, V0, V1 in flight
-        } else {
-            issue_v(2);
-            AT_WAIT_VM(3 * NV3);                     // K2 landed; V0, V1, V2 in flight
+        if constexpr (!RESIDENT) {
+            if (G == 0) {
+                AT_WAIT_VM(2 * NKP);                     // K0 landed; K1, K2 may be in flight
+            } else if (G == 1) {
+                issue_v(0);
+                issue_v(1);
+                AT_WAIT_VM(NKP + 2 * NV3);               // K1 landed; K2, V0, V1 in flight
+            } else {
+                issue_v(2);
+                AT_WAIT_VM(3 * NV3);                     // K2 landed; V0, V1, V2 in flight
+            }
+            __builtin_amdgcn_s_barrier();
         }
-        __builtin_amdgcn_s_barrier();
         AT_STAMP(2 + G);
         auto kread = [&](f32x4* kf, int ks) {
 #pragma unroll
@@ -272,7 +296,7 @@ __device__ __forceinline__ void attention_item(const float* __restrict__ qkv, fl
     }
 
     AT_STAMP(6);
-    AT_WAIT_VM(0);                       // V has landed
+    if constexpr (!RESIDENT) AT_WAIT_VM(0);      // V has landed
     __builtin_amdgcn_s_barrier();        // ... for every wave; and every wave is done reading K
     AT_STAMP(7);
 
@@ -291,7 +315,7 @@ __device__ __forceinline__ void attention_item(const float* __restrict__ qkv, fl
                 if (kb < AT_NB) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const f32x4 vf = *reinterpret_cast<const f32x4*>(Vs + (kb * 16 + lg * 4 + j) * AT_DH + db * 64 + li * 4);
+                        const f32x4 vf = *reinterpret_cast<const f32x4*>(vaddr(kb * 16 + lg * 4 + j, db));
 #pragma unroll
                         for (int m = 0; m < 4; ++m)
                             oacc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(cs[t][j], vf[m], oacc[m], 0, 0, 0);
@@ -325,7 +349,7 @@ __device__ __forceinline__ void attention_item(const float* __restrict__ qkv, fl
 #pragma unroll
             for (int m = 0; m < 4; ++m) oacc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
             auto vread = [&](int st) {      // step st = 4 kb + j: keys 16 kb + 4 g + j
-                return *reinterpret_cast<const f32x4*>(Vs + ((st >> 2) * 16 + lg * 4 + (st & 3)) * AT_DH + db * 64 + li * 4);
+                return *reinterpret_cast<const f32x4*>(vaddr((st >> 2) * 16 + lg * 4 + (st & 3), db));
             };
             // steps are taken in pairs (8 MFMAs); the two reads of the next pair go out behind the first MFMA
             f32x4 vf[2][2];

@@ -54,9 +54,15 @@ struct PhaseArgs {
     unsigned* err; unsigned xcc1; int fault;
 };
 
-// Issue the first two K chunks of a phase's weight tile (rows n0 .. n0 + BN of W) into the two W buffers: 2 x BN * 8 / 256 LDS-DMA
-// instructions per wave, no register staging.  Called while the PREVIOUS phase's epilogue is still to run.
-template <int BN>
+// The head-aligned in-projection tile of the stack at 4 parts per clip (HEAD): part tn computes the q | k | v columns of head tn, so
+// that its attention item needs nothing of its partners.  Tile column t is dim 32 (t / 96) + t % 32 of segment (t % 96) / 32 (q, k,
+// v) of the head whose first column is n0 = 128 tn: wave w's 96 columns are dims 32 w .. 32 w + 31 of q, of k and of v.  Every
+// output element is the same dot product in the same k order as in the 384-column slice of the plain tile.
+__device__ __forceinline__ int head_row(int n0, int t) { return ((t % 96) >> 5) * 512 + n0 + (t / 96) * 32 + (t & 31); }
+
+// Issue the first two K chunks of a phase's weight tile (rows n0 .. n0 + BN of W, or HEAD's rows) into the two W buffers:
+// 2 x BN * 8 / 256 LDS-DMA instructions per wave, no register staging.  Called while the PREVIOUS phase's epilogue is still to run.
+template <int BN, bool HEAD = false>
 __device__ __forceinline__ void prefetch_w(const float* W, int ldw, int n0, float* smem, int tid, int wave_u) {
     constexpr int B_ITERS = BN * 8 / 256;
     float* Bs = smem + 2 * BM * BK;
@@ -67,7 +73,7 @@ __device__ __forceinline__ void prefetch_w(const float* W, int ldw, int n0, floa
             const int u = tid + i * 256;
             const int row = u >> 3;
             const int slot = (u & 7) ^ ((row >> 1) & 7);
-            const float* src = W + (size_t)(n0 + row) * ldw + slot * 4 + buf * BK;
+            const float* src = W + (size_t)(HEAD ? head_row(n0, row) : n0 + row) * ldw + slot * 4 + buf * BK;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(Bs + buf * (BN * BK) + (i * 256 + wave_u) * 4), 16, 0, 0);
         }
@@ -111,9 +117,14 @@ __device__ __forceinline__ void group_sync(unsigned long long* flags, int tn, in
 // One tile of one phase: C[m0.., n0..n0+BN) = epi(A[m0.., :K] . W[n0.., :K]^T).  PREF: the first two W chunks are in LDS (or on
 // their way) already; SC1: A was written by partner workgroups of this launch -- fetch it from L2, never from this CU's L1.
 // `after_loop()` runs once all waves are done with the staging buffers (the place to start the next phase's weights).
-template <int BN, int EPI, bool PREF, bool SC1, bool REFETCH, typename AfterLoop>
-__device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, const int tid, AfterLoop&& after_loop) {
+// HEAD (EPI_QKV, 384 columns, the stack at 4 parts per clip): the head-aligned tile (head_row; p.n0 = the head's first column), whose
+// epilogue hands q, k and v to the attention item through LDS instead of storing them: K into attention's K image, V into its V image
+// (both XOR-swizzled: attention_item's RESIDENT layout) and the Q fragments into *q_out.  The caller's next barrier publishes V.
+template <int BN, int EPI, bool PREF, bool SC1, bool REFETCH, bool HEAD = false, typename AfterLoop>
+__device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, const int tid, AfterLoop&& after_loop,
+                                           AtQFrags<2>* q_out = nullptr) {
     static_assert(EPI == EPI_BIAS_RES_LN || EPI == EPI_BIAS_GELU || EPI == EPI_QKV || EPI == EPI_EMBED, "chain phases: LN tail, GELU, QKV, embed");
+    static_assert(!HEAD || (EPI == EPI_QKV && BN == 3 * AT_DH), "the head-aligned tile is one head's q | k | v");
     constexpr int WN = BN / 4;
     // Every phase on v_mfma_f32_16x16x4_f32.  gemm_f32.hip's own launches run rows 0..127 of their 256- / 384-wide tiles on
     // v_mfma_f32_32x32x2_f32 (half the operand-register traffic per flop; measured faster there in round 2); INSIDE the stack the
@@ -128,6 +139,10 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
     float* Bs = smem + 2 * BM * BK;
     float* lds_dummy = smem + kZone;
     float* const zone = lds_dummy + 512;          // statistics of the LayerNorm tail / bias row of the 384-wide tile
+    // HEAD: the bias row sits behind attention's K and V images (over its DMA dummy and statistics words, unused until the item's
+    // cooperative block), so that the handoff may overwrite the zone
+    float* const colrow = HEAD ? smem + 2 * AT_TILE : zone;
+    static_assert(!HEAD || 2 * AT_TILE + 512 <= AT_LDS_FLOATS, "head-aligned tile: the bias row overruns the stack's LDS");
 
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -150,7 +165,7 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
         const int u = tid + i * 256;
         const int row = u >> 3;
         const int slot = (u & 7) ^ ((row >> 1) & 7);
-        b_src[i] = p.W + (size_t)(n0 + row) * p.ldw + slot * 4;
+        b_src[i] = p.W + (size_t)(HEAD ? head_row(n0, row) : n0 + row) * p.ldw + slot * 4;
     }
     auto dma_a = [&](int buf, int k0) {
 #pragma unroll
@@ -205,9 +220,10 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int unit = h * 64 + lane;
-                const float* src = p.bias + n0 + (unit < BN / 4 ? unit : BN / 4 - 1) * 4;
+                const int t = (unit < BN / 4 ? unit : BN / 4 - 1) * 4;
+                const float* src = HEAD ? p.bias + head_row(n0, t) : p.bias + n0 + t;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(zone + h * 256), 16, 0, 0);
+                                                 (__attribute__((address_space(3))) void*)(colrow + h * 256), 16, 0, 0);
             }
         }
     }
@@ -228,7 +244,7 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
     auto load_col = [&](int nb) __attribute__((always_inline)) {
         ColOps o{zero4, zero4, zero4};
         if constexpr (EPI == EPI_EMBED) { /* the biases are part of the table rows */ }
-        else if constexpr (COL_LDS) o.bias = *reinterpret_cast<const f32x4*>(zone + (nb - n0));
+        else if constexpr (COL_LDS) o.bias = *reinterpret_cast<const f32x4*>(colrow + (nb - n0));
         else o.bias = *reinterpret_cast<const f32x4*>(p.bias + nb);
         if constexpr (RES) {
             o.g4 = *reinterpret_cast<const f32x4*>(p.gamma + nb);
@@ -443,6 +459,41 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
                 *reinterpret_cast<f32x4*>(p.C + (size_t)(m0 + r * 16 + li) * p.ldc + nw + c * 16 + lg * 4) = v;
             }
         }
+    } else if constexpr (HEAD) {
+        // Column block c of a wave: segment c / 2 (q, k, v), dims 32 wave + 16 (c & 1) + 4 lg .. + 3 = unit u of the head's 32, for the
+        // tokens r * 16 + li.  Stored with K's swizzle (unit u ^ (token & 15)): the 8-lane groups of a ds_write_b128 hit 8 distinct
+        // 16-byte slots (unswizzled they would share one: 8-way).  Q goes into the V image first, each wave reads its fragments, then
+        // V replaces it.
+        float* const Ks = smem;
+        float* const Vs = smem + AT_TILE;
+        auto put = [&](float* img, int c) __attribute__((always_inline)) {
+            const int u = wave * 8 + (c & 1) * 4 + lg;
+#pragma unroll
+            for (int r = 0; r < NRB; ++r) {
+                const f32x4 a = acc16[r * NCB + c];
+                f32x4 v;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = a[q] + col[c].bias[q];
+                if (c < 2) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[q] *= p.qscale;
+                }
+                *reinterpret_cast<f32x4*>(img + (r * 16 + li) * AT_DH + ((u ^ li) << 2)) = v;
+            }
+        };
+        put(Vs, 0); put(Vs, 1);
+        put(Ks, 2); put(Ks, 3);
+        __syncthreads();
+        // attention_item's fragments at 4 waves, two owned blocks each: queries (ps * 4 + wave) * 16 + li, and the cooperative block 8
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+            const int sw = ((ks * 4 + lg) ^ li) << 2;
+#pragma unroll
+            for (int ps = 0; ps < 2; ++ps) q_out->f[ps][ks] = *reinterpret_cast<const f32x4*>(Vs + ((ps * 4 + wave) * 16 + li) * AT_DH + sw);
+            q_out->c[ks] = *reinterpret_cast<const f32x4*>(Vs + (8 * 16 + li) * AT_DH + sw);
+        }
+        __syncthreads();
+        put(Vs, 4); put(Vs, 5);
     } else if constexpr (EPI == EPI_EMBED) {
         for_units([&](int i, int, int m, int nb, f32x4 a) __attribute__((always_inline)) {
             const int tok = m % p.S;
@@ -735,6 +786,8 @@ __global__ __launch_bounds__(256) void encoder_chain_kernel(ChainParams p) {
 // per wave) or half tn & 1 of head tn >> 1 (G = 8: the SPLIT shape of attention_f32.hip), then its column tile of every GEMM phase.
 // Every operand another workgroup wrote earlier in THIS launch is fetched past the L1 (sc1 LDS-DMA): the same addresses were read one
 // layer earlier.  Two leading phases turn the packed input into h and layer 0's qkv first (InputProcess + in_proj_0).
+// G = 4: the in-projection tile of part tn is head tn's q | k | v (gemm_phase HEAD), handed to the attention item through LDS -- qkv
+// is neither stored nor read, and no meeting precedes attention.
 template <int G>
 __global__ __launch_bounds__(256) void encoder_stack_kernel(StackParams p) {
     using namespace chain;
@@ -753,10 +806,32 @@ __global__ __launch_bounds__(256) void encoder_stack_kernel(StackParams p) {
     a.row_stats = p.xln_stats + ((size_t)g * G * BM) * 4;
     a.eps = p.ln_eps; a.ln_dim = p.D;
     a.qcols = p.D; a.qscale = p.qscale;
+    constexpr bool HEAD = G == 4;
+    // first column of the in-projection tile (HEAD: of head tn), computed where it is used (as a hoisted value it moves G = 8 code)
+    auto n0q = [&]() __attribute__((always_inline)) { return HEAD ? tn * AT_DH : tn * BNQ; };
+    AtQFrags<2> qh;      // HEAD: the Q fragments the in-projection hands to the next attention item
     // diagnostics only (p.timeline is null on every product path: one scalar test per seam)
     unsigned long long* const tl = p.timeline ? p.timeline + (size_t)blockIdx.x * kStackTimelineLayers * kStackTimelineStamps : nullptr;
     auto stamp = [&](int layer, int k) __attribute__((always_inline)) {
         if (tl != nullptr && threadIdx.x == 0) tl[layer * kStackTimelineStamps + k] = __builtin_amdgcn_s_memrealtime();
+    };
+    // Layer l's attention item and the meeting behind it (the clip's ctx is complete).  HEAD: directly behind the in-projection that
+    // handed it q, k and v -- layer 0's ahead of the loop, layer l + 1's at the end of iteration l -- so that the Q fragments live
+    // from one to the other only (carried round the loop, they spilled 136 VGPRs)
+    auto attend = [&](int l, int tid) __attribute__((always_inline)) {
+        unsigned long long* const fl = p.flags + ((size_t)g * 9 + l) * 5 * 8;
+        stamp(l, 0);
+        if (l > 0) {
+            if constexpr (HEAD) __syncthreads();                                     // the head's K and V images are complete
+            else group_sync(fl, tn, G, ep, xcc1, p.xln_err, tid);                    // the clip's qkv of this layer is complete
+        }
+        stamp(l, 1);
+        if constexpr (HEAD)
+            attention_item<4, 0, kSc1, 2, true>(p.qkv, p.ctx, p.n_head, g * p.n_head + tn, 0, AT_NB, smem, tid, &qh);
+        else attention_item<4, 0, kSc1, 1>(p.qkv, p.ctx, p.n_head, g * p.n_head + (tn >> 1), (tn & 1) ? 5 : 0, (tn & 1) ? 4 : 5, smem, tid);
+        stamp(l, 2);
+        group_sync(fl + 8, tn, G, ep, xcc1, p.xln_err, tid);                         // ... its ctx
+        stamp(l, 3);
     };
     {
     // ---- E: h = [x_t | cond] . We^T + table rows;  D0: qkv = in_proj_0(h) -- flags of "layer" 8 ------------------------------------
@@ -767,16 +842,18 @@ __global__ __launch_bounds__(256) void encoder_stack_kernel(StackParams p) {
     a.A = p.apack; a.lda = p.lda_pack; a.W = p.w_embed; a.ldw = p.ldw_embed; a.C = p.h; a.ldc = p.D; a.K = p.k_embed; a.n0 = tn * BNL;
     a.S = p.S; a.tab = p.tab; a.tab0 = p.tab0; a.ldtab = p.ldtab; a.ldtab0 = p.ldtab0; a.tab_by_row = p.tab_by_row;
     stamp(8, 0);
-    gemm_phase<BNL, EPI_EMBED, false, false, G == 8>(a, smem, tid, [&]() { prefetch_w<BNQ>(p.layer[0].in_w, p.D, tn * BNQ, smem, tid, wave_u); });
+    gemm_phase<BNL, EPI_EMBED, false, false, G == 8>(a, smem, tid, [&]() { prefetch_w<BNQ, HEAD>(p.layer[0].in_w, p.D, n0q(), smem, tid, wave_u); });
     stamp(8, 1);
     group_sync(fl, tn, G, ep, xcc1, p.xln_err, tid);
     stamp(8, 2);
     a.A = p.h; a.lda = p.D; a.W = p.layer[0].in_w; a.ldw = p.D; a.C = p.qkv; a.ldc = 3 * p.D; a.K = p.D; a.bias = p.layer[0].in_b;
-    a.n0 = tn * BNQ;
-    gemm_phase<BNQ, EPI_QKV, true, true, G == 8>(a, smem, tid, []() {});
+    a.n0 = n0q();
+    gemm_phase<BNQ, EPI_QKV, true, true, G == 8, HEAD>(a, smem, tid, []() {}, &qh);
     stamp(8, 3);
-    group_sync(fl + 8, tn, G, ep, xcc1, p.xln_err, tid);
+    if constexpr (HEAD) __syncthreads();      // this workgroup's K and V images are complete: its attention item needs nothing else
+    else group_sync(fl + 8, tn, G, ep, xcc1, p.xln_err, tid);
     stamp(8, 4);
+    if constexpr (HEAD) attend(0, tid);
     }
 #pragma unroll 1
     for (int l = 0; l < p.L; ++l) {
@@ -788,14 +865,7 @@ __global__ __launch_bounds__(256) void encoder_stack_kernel(StackParams p) {
         const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6) * 64;
         const StackLayerW& w = p.layer[l];
         unsigned long long* const fl = p.flags + ((size_t)g * 9 + l) * 5 * 8;
-        stamp(l, 0);
-        if (l > 0) group_sync(fl, tn, G, ep, xcc1, p.xln_err, tid);                  // the clip's qkv of this layer is complete
-        stamp(l, 1);
-        if constexpr (G == 4) attention_item<4, 0, kSc1, 2>(p.qkv, p.ctx, p.n_head, g * p.n_head + tn, 0, AT_NB, smem, tid);
-        else attention_item<4, 0, kSc1, 1>(p.qkv, p.ctx, p.n_head, g * p.n_head + (tn >> 1), (tn & 1) ? 5 : 0, (tn & 1) ? 4 : 5, smem, tid);
-        stamp(l, 2);
-        group_sync(fl + 8, tn, G, ep, xcc1, p.xln_err, tid);                         // ... its ctx
-        stamp(l, 3);
+        if constexpr (!HEAD) attend(l, tid);
 
         a.A = p.ctx; a.lda = p.D; a.W = w.out_w; a.ldw = p.D; a.C = p.y; a.ldc = p.D; a.K = p.D; a.bias = w.out_b;
         a.R = p.h; a.ldr = p.D; a.gamma = w.n1_w; a.beta = w.n1_b; a.n0 = tn * BNL; a.tag28 = (ep + 4u * l) & 0x0fffffffu;
@@ -815,7 +885,7 @@ __global__ __launch_bounds__(256) void encoder_stack_kernel(StackParams p) {
         a.A = p.ff; a.lda = p.F; a.W = w.l2_w; a.ldw = p.F; a.C = p.h; a.ldc = p.D; a.K = p.F; a.bias = w.l2_b;
         a.R = p.y; a.ldr = p.D; a.gamma = w.n2_w; a.beta = w.n2_b; a.n0 = tn * BNL; a.tag28 = (ep + 4u * l + 1u) & 0x0fffffffu;
         a.fault = (l == 0) ? ((p.fault >> 1) & 1) : 0;
-        gemm_phase<BNL, EPI_BIAS_RES_LN, true, true, G == 8>(a, smem, tid, [&]() { if (more) prefetch_w<BNQ>(p.layer[l + 1].in_w, p.D, tn * BNQ, smem, tid, wave_u); });
+        gemm_phase<BNL, EPI_BIAS_RES_LN, true, true, G == 8>(a, smem, tid, [&]() { if (more) prefetch_w<BNQ, HEAD>(p.layer[l + 1].in_w, p.D, n0q(), smem, tid, wave_u); });
         stamp(l, 8);
         if (!more) {
             if (p.tail) {      // sampling loop: head + DDPM update + the next step's pack close the launch (uniform over the launch)
@@ -833,9 +903,10 @@ __global__ __launch_bounds__(256) void encoder_stack_kernel(StackParams p) {
         stamp(l, 9);
 
         a.A = p.h; a.lda = p.D; a.W = p.layer[l + 1].in_w; a.ldw = p.D; a.C = p.qkv; a.ldc = 3 * p.D; a.K = p.D; a.bias = p.layer[l + 1].in_b;
-        a.n0 = tn * BNQ;
-        gemm_phase<BNQ, EPI_QKV, true, true, G == 8>(a, smem, tid, []() {});
+        a.n0 = n0q();
+        gemm_phase<BNQ, EPI_QKV, true, true, G == 8, HEAD>(a, smem, tid, []() {}, &qh);
         stamp(l, 10);
+        if constexpr (HEAD) attend(l + 1, tid);
     }
 }
 
