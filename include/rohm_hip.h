@@ -436,6 +436,19 @@ int rohm_repr_joints(const rohm_smplx_t* h, const float* repr, long long in_stri
                      long long in_stride_c, const float* mean294, const float* std294, int B, int T, int mode,
                      float* joints, rohm_stream_t stream);
 
+/* Vector-Jacobian product of rohm_repr_joints: the same recovery arguments, plus d_joints [B,T,22,3] (dL/djoints,
+ * contiguous).  Writes dL/drepr into d_repr, element (b, t, c) at d_repr[b*out_stride_b + t*out_stride_t +
+ * c*out_stride_c], for all 294 channels (0 on those the mode does not read); with mean294/std294 this is the gradient
+ * with respect to the NORMALISED input (the de-normalisation's factor std included).  Used to backpropagate the joint
+ * terms of PoseNet.compute_losses_with_smpl (model/posenet.py:98-194) into the network output.  mode 0 differentiates
+ * the Gram-Schmidt matrices directly: the reference's R -> axis-angle -> Rodrigues round trip is the identity on SO(3).
+ * mode 2 runs the running sums over frames backwards (T <= 2048).  No atomics: bitwise reproducible.  d_repr must not
+ * overlap repr. */
+int rohm_repr_joints_vjp(const rohm_smplx_t* h, const float* repr, long long in_stride_b, long long in_stride_t,
+                         long long in_stride_c, const float* mean294, const float* std294, int B, int T, int mode,
+                         const float* d_joints, float* d_repr, long long out_stride_b, long long out_stride_t,
+                         long long out_stride_c, rohm_stream_t stream);
+
 /* Between-stage trajectory re-derivation: replaces the drivers' host round trip
  * test_amass_full.py:262-311 / test_prox_egobody.py:238-287 -- de-normalise TrajNet's representation,
  * recover_from_repr_smpl('smplx_params') (data_loaders/motion_representation.py:373-398), per-sequence

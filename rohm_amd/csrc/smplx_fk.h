@@ -149,7 +149,9 @@ __device__ __forceinline__ void fk_forward(FkCtx& f, const int* __restrict__ par
 }
 
 // Reverse pass of fk_forward.  gP[j] = dL/dP[j] on entry (overwritten).  Outputs dR[j] (dL/dR_j, j >= 1; the
-// global orientation lives in a zeroed channel range) and dJr (dL/dJrest).
+// global orientation lives in a zeroed channel range) and dJr (dL/dJrest).  kRootRot also writes dR[0] (G[0] = R[0]):
+// the joint-recovery VJP (repr_joints_vjp.hip) needs it, the guidance kernels do not.
+template <bool kRootRot = false>
 __device__ __forceinline__ void fk_backward(const FkCtx& f, const int* __restrict__ parents, float (*gP)[3],
                                             float (*dR)[9], float (*dJr)[3]) {
     float dG[NJ][9];
@@ -192,6 +194,10 @@ __device__ __forceinline__ void fk_backward(const FkCtx& f, const int* __restric
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) dJr[0][c] += gP[0][c];
+    if constexpr (kRootRot) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) dR[0][i] = dG[0][i];
+    }
 }
 
 // Loads + de-normalises the channels the SMPL-X path needs for frame (b, t) and runs FK.

@@ -58,15 +58,24 @@ def _strides(x, layout):
     raise ValueError(f'unknown layout {layout!r}')
 
 
-def joints_from_repr(repr_full, recover_mode='smplx_params', smplx_model=None, stats=None, layout='btc'):
-    """[B,T,22,3] joints from the full 294-channel representation (any strides, no copy).  `stats` = dataset or
-    (mean, std) to de-normalise on the fly, None if `repr_full` is already de-normalised."""
-    if recover_mode not in _MODES:
-        raise ValueError(f'recover_mode {recover_mode!r} is not supported (joint_abs_traj | joint_rel_traj | smplx_params)')
-    _lib.require_hip(repr_full)
-    x = repr_full.detach()
-    if x.dtype != torch.float32:
-        x = x.float()
+class _ReprJoints(torch.autograd.Function):
+    """joints_from_repr with its backward on the device (rohm_repr_joints_vjp)."""
+
+    @staticmethod
+    def forward(ctx, x, recover_mode, smplx_model, stats, layout):
+        ctx.save_for_backward(x)
+        ctx.args = (recover_mode, smplx_model, stats, layout)
+        return _joints(x, recover_mode, smplx_model, stats, layout)
+
+    @staticmethod
+    def backward(ctx, d_joints):
+        (x,) = ctx.saved_tensors
+        return joints_vjp(x, d_joints, *ctx.args), None, None, None, None
+
+
+def _native_args(x, recover_mode, smplx_model, stats, layout):
+    """(recovery arguments of the C ABI, (mean, std)): the caller holds the second until the launch is enqueued, so that
+    the allocator cannot hand freshly converted statistics to the output buffer."""
     B, T, sb, st, sc = _strides(x, layout)
     dev = x.device
     handle = None
@@ -77,11 +86,51 @@ def joints_from_repr(repr_full, recover_mode='smplx_params', smplx_model=None, s
     mean = std = None
     if stats is not None:
         mean, std = _stats(stats, dev)
-    out = torch.empty(B, T, 22, 3, device=dev, dtype=torch.float32)
-    check(lib().rohm_repr_joints(handle, x.data_ptr(), sb, st, sc, ptr(mean) if mean is not None else None,
-                                 ptr(std) if std is not None else None, B, T, _MODES[recover_mode], ptr(out),
-                                 stream_ptr(dev)), 'rohm_repr_joints')
+    return (handle, x.data_ptr(), sb, st, sc, ptr(mean) if mean is not None else None,
+            ptr(std) if std is not None else None, B, T, _MODES[recover_mode]), (mean, std)
+
+
+def _joints(x, recover_mode, smplx_model, stats, layout):
+    args, _keep = _native_args(x, recover_mode, smplx_model, stats, layout)
+    out = torch.empty(args[7], args[8], 22, 3, device=x.device, dtype=torch.float32)
+    check(lib().rohm_repr_joints(*args, ptr(out), stream_ptr(x.device)), 'rohm_repr_joints')
     return out
+
+
+def joints_vjp(repr_full, d_joints, recover_mode='smplx_params', smplx_model=None, stats=None, layout='btc'):
+    """dL/d`repr_full` (float32, same shape and layout, all 294 channels) given dL/djoints [B,T,22,3]: the
+    backward of `joints_from_repr` on the device (rohm_repr_joints_vjp)."""
+    if recover_mode not in _MODES:
+        raise ValueError(f'recover_mode {recover_mode!r} is not supported (joint_abs_traj | joint_rel_traj | smplx_params)')
+    _lib.require_hip(repr_full, d_joints)
+    x = repr_full.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    args, _keep = _native_args(x, recover_mode, smplx_model, stats, layout)
+    B, T = args[7], args[8]
+    if tuple(d_joints.shape) != (B, T, 22, 3):
+        raise ValueError(f'd_joints must be [{B}, {T}, 22, 3], got {tuple(d_joints.shape)}')
+    dj = d_joints.detach().float().contiguous()
+    dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    _, _, osb, ost, osc = _strides(dx, layout)
+    check(lib().rohm_repr_joints_vjp(*args, ptr(dj), ptr(dx), osb, ost, osc, stream_ptr(x.device)), 'rohm_repr_joints_vjp')
+    return dx
+
+
+def joints_from_repr(repr_full, recover_mode='smplx_params', smplx_model=None, stats=None, layout='btc'):
+    """[B,T,22,3] joints from the full 294-channel representation (any strides, no copy).  `stats` = dataset or
+    (mean, std) to de-normalise on the fly, None if `repr_full` is already de-normalised.  Differentiable with respect
+    to `repr_full` when it requires grad and grad mode is on (backward: `joints_vjp`); detached otherwise."""
+    if recover_mode not in _MODES:
+        raise ValueError(f'recover_mode {recover_mode!r} is not supported (joint_abs_traj | joint_rel_traj | smplx_params)')
+    _lib.require_hip(repr_full)
+    if repr_full.requires_grad and torch.is_grad_enabled():
+        x = repr_full if repr_full.dtype == torch.float32 else repr_full.float()
+        return _ReprJoints.apply(x, recover_mode, smplx_model, stats, layout)
+    x = repr_full.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    return _joints(x, recover_mode, smplx_model, stats, layout)
 
 
 def recover_from_repr_smpl(data_dict, recover_mode='joint_abs_traj', smplx_model=None, return_verts=False,

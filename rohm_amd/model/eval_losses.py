@@ -3,8 +3,9 @@ test_posenet.py:178 / test_trajnet.py:154): `PoseNet.compute_losses_with_smpl` (
 `TrajNet.compute_losses_with_smpl` (model/trajnet.py:277-400), forward only.
 
 The joints come from the HIP kernels (`rohm_repr_joints`, all three recover modes, de-normalising on the fly); what
-remains are means of squared differences over small tensors, done with device tensor reductions.  No gradients: these
-are reports, training is outside the path.  Pinned to the reference's own methods by tests/golden/eval_losses.npz.
+remains are means of squared differences over small tensors, done with device tensor reductions.  When model_output
+requires grad, `loss` backpropagates into it: the joint recoveries' backward is `rohm_repr_joints_vjp`; the values
+reported are the same either way.  Pinned to the reference's own methods by tests/golden/eval_losses.npz.
 """
 from __future__ import annotations
 

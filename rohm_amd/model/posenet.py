@@ -355,6 +355,6 @@ class PoseNet(nn.Module):
         return guide_2d_projection(self, batch, out, denoise_t, compute_grad)
 
     def compute_losses_with_smpl(self, batch, model_output, smplx_model=None, epoch=0):
-        """Evaluation loss report (model/posenet.py:98-194), forward only."""
+        """Loss dict of model/posenet.py:98-194; `loss` backpropagates into `model_output` when it requires grad."""
         from .eval_losses import posenet_losses
         return posenet_losses(self, batch, model_output, smplx_model, epoch)
