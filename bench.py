@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: denoised 145-frame clips/s at 1000 DDPM steps (BASELINE.json `metric`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--ddpm-steps 1000] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--ddpm-steps 1000] [--dump-outputs DIR] [--full]
 
 One "step" = one complete pass of the hot path over one batch: a full PoseNet `eval_losses` run
 (x_T -> x_0 through 1000 ancestral DDPM steps, on-device noise generation included) for `--batch`
@@ -16,18 +16,25 @@ given.  A world size that disagrees with --gpus, or fewer visible GPUs than rank
 1-rank run.
 
 Rank 0 prints ONE JSON line (contract in the task statement) carrying `roofline` (the fp32-MFMA GEMM
-family: algorithmic flops / HIP-event-measured launch time, sampled every 16th denoising step of the
-timed region on the launch stream) and, at N = 1, `cpu_baseline` (the reference's own p_sample on its own PoseNet where
-/root/reference exists -- the build container -- else the CPU oracle port of the same step, timed on the host cores).
+family: algorithmic flops / HIP-event-measured launch time, sampled every `--profile-stride`-th denoising step of the
+timed region on the launch stream).  A plain run stops there: set up, warm up, time the K passes, write `--dump-outputs`,
+print the line.
 
-At N = 1 the default run then adds, each measured by a child process AFTER the headline leg (thermal history: the headline
-always runs first on a cold chip) and none of them ever replacing `value` / `dtype` / `roofline`, which stay exact fp32:
+`--full` adds every measurement that costs time of its own after the timed passes (see `legs()`):
+  `roofline.attention`  the attention phase inside the encoder-stack launch from its phase stamps (+ `attention_standalone`);
+  `cpu_baseline` (N = 1)  the reference's own p_sample on its own PoseNet where the reference tree is importable, else the
+                 CPU oracle port of the same step, timed on the host cores;
+  `accuracy` (N = 1)  one clip through 1000 DDPM steps against the reference's own run (tests/golden/posenet_loop1000.npz);
+and then, at N = 1, each measured by a child process AFTER the headline leg (thermal history: the headline always runs first on
+a cold chip) and none of them ever replacing `value` / `dtype` / `roofline`, which stay exact fp32:
   `second_line`  the same workload under ROHM_GEMM_PRECISION=fp16x3 (split GEMMs on fp16 planes) with its own dtype,
                  roofline (fp16 MFMA peak / 3) and 1000-step accuracy against the reference's own run (+ `also.bf16x6`);
   `configs`      one short pass each of the other BASELINE.json configurations on this GPU: `b32` (PoseNet at the per-GPU
                  batch of configs[2..4]), `scheme_b32` (configs[2]), `prox_b32` (configs[3]), `egobody_b32` (configs[4]).
-`--no-extras` skips both (the children run with it).  `--force-dist` initialises the RCCL process group even at world size
-1 and runs the barrier / MAX all-reduce / result all-gather of the multi-GPU path through it.
+Under `--full`, `--no-extras` skips the children and `--no-cpu-baseline` the CPU leg and the accuracy record (the children run
+with `--full --no-extras --no-cpu-baseline`); `--with-accuracy` / `--config-cpu-baseline` ask for those two legs in any run.
+`--force-dist` initialises the RCCL process group even at world size 1 and runs the barrier / MAX all-reduce / result all-gather
+of the multi-GPU path through it.
 """
 from __future__ import annotations
 
@@ -357,6 +364,19 @@ def cpu_baseline_config(workload, B, budget_s=18.0):
             'torch_threads': torch.get_num_threads()}
 
 
+def legs(args, world):
+    """Which measurements rank 0 adds after the timed passes.  A plain run adds none: its line carries what the timed passes
+    themselves measured.  `--full` adds the in-stack attention figures at any world size and, at N = 1, the CPU baseline, the
+    1000-step accuracy record (PoseNet only) and the child measurements (exact-fp32 PoseNet only); `--no-cpu-baseline` /
+    `--no-extras` thin a full run, `--config-cpu-baseline` / `--with-accuracy` ask for their leg in any run."""
+    one, posenet = world == 1, args.workload == 'posenet'
+    cpu_leg = args.full and not args.no_cpu_baseline
+    return {'attention': args.full,
+            'cpu_baseline': one and (cpu_leg or args.config_cpu_baseline),
+            'accuracy': one and posenet and (cpu_leg or args.with_accuracy),
+            'extras': one and posenet and args.full and not args.no_extras and not _PRODUCTS}
+
+
 class _TrajDataset(_Dataset):
     traj_feat_dim = 13
 
@@ -490,7 +510,7 @@ def scheme_bench(args, world, rank, dev, dist):
         rec['rank_report'] = report
         if args.dump_outputs:
             rec['dump_outputs'] = dumped
-        if world == 1 and (not args.no_cpu_baseline or args.config_cpu_baseline):
+        if legs(args, world)['cpu_baseline']:
             try:
                 rec['cpu_baseline'] = cpu_baseline_config(args.workload, B)
             except Exception as e:      # a side measurement never costs the record
@@ -532,7 +552,7 @@ def run_child(argv, env_extra=None, timeout=600):
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'ROHM_GEMM_PRECISION'):
         env.pop(k, None)
     env.update(env_extra or {})
-    cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--no-extras', '--no-cpu-baseline'] + list(argv)
+    cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--full', '--no-extras', '--no-cpu-baseline'] + list(argv)
     t0 = time.perf_counter()
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
@@ -1002,7 +1022,10 @@ def main(argv=None):
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--batch', type=int, default=64, help='clips per GPU')
     ap.add_argument('--ddpm-steps', type=int, default=1000)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure what takes time of its own (legs()): the in-stack attention figures, the '
+                         'CPU baseline, the 1000-step accuracy record and, at N = 1, the second_line / configs children')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline and the accuracy record')
     ap.add_argument('--config-cpu-baseline', action='store_true',
                     help='attach the CPU baseline of THIS workload even under --no-cpu-baseline (what the parent record asks of its configs children)')
     ap.add_argument('--backend', choices=['nccl', 'gloo'], default='nccl',
@@ -1019,7 +1042,7 @@ def main(argv=None):
                          'records around each of a step\'s 51 launches cost ~0.5 ms per sampled step: at N = 16 (rounds 1-4) that was 1 %% of '
                          'the headline value and 2.7 %% of the scheme workloads; at N = 100 it is 0.16 %% and still times 160 launches of the '
                          'dominant kernel per 1000-step pass')
-    ap.add_argument('--no-extras', action='store_true', help='N = 1 only: skip the second_line / configs child measurements')
+    ap.add_argument('--no-extras', action='store_true', help='with --full at N = 1: skip the second_line / configs child measurements')
     ap.add_argument('--with-accuracy', action='store_true', help='attach the 1000-step accuracy record even without the CPU leg')
     ap.add_argument('--guidance-semantics', choices=['replica', 'global'], default='replica',
                     help="guided workloads under clip sharding (SURVEY.md §8(e)): 'replica' = every rank behaves like the reference at "
@@ -1099,6 +1122,7 @@ def main(argv=None):
     finite = bool(torch.isfinite(out).all())
     assert finite, 'non-finite samples'
     report = rank_report(args, world, rank, dev, dist, gather, net)
+    run = legs(args, world)
 
     if rank == 0:
         if args.dump_outputs:      # a multi-rank caller receives every rank's clips (the all-gather)
@@ -1165,15 +1189,17 @@ def main(argv=None):
                                 'the build named by traffic_source), not collected by this run',
                 'mfma_busy_pmc': pmc_mfma(B),
                 # north_star: "... as fraction of the attention/GEMM roofline": the attention kernel by the same event timing -- or,
-                # when attention runs INSIDE the encoder-stack launch (no launch of its own to time), the same kernel launched on its
-                # own right after the timed region
+                # when attention runs INSIDE the encoder-stack launch (no launch of its own to time), its phase stamps on a few
+                # launches right after the timed region (--full only: None in a plain run)
                 'attention': ({'achieved': prof['attention']['flops'] / (prof['attention']['total_ms'] * 1e-3) / 1e12,
                                'frac': prof['attention']['flops'] / (prof['attention']['total_ms'] * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS,
                                'avg_launch_us': prof['attention']['total_ms'] / prof['attention']['launches'] * 1e3,
                                'unit': 'TFLOP/s', 'peak': PEAK_F32_MFMA_TFLOPS}
-                              if prof.get('attention', {}).get('total_ms') else in_stack_attention(net, B, dev)),
+                              if prof.get('attention', {}).get('total_ms') else
+                              in_stack_attention(net, B, dev) if run['attention'] else None),
                 # ... and the stand-alone attention kernel (the launch shape of the launch-per-GEMM path) for comparison
-                'attention_standalone': (None if prof.get('attention', {}).get('total_ms') or _PRODUCTS else standalone_attention(B, dev)),
+                'attention_standalone': (None if prof.get('attention', {}).get('total_ms') or _PRODUCTS or not run['attention'] else
+                                         standalone_attention(B, dev)),
                 # the dominant kernel on its own (VERDICT convention: algorithmic flops per launch / average launch duration)
                 'dominant': ({'kernel': ('encoder_stack_kernel (label gemm_stack_tail: the WHOLE denoising step -- input embedding, the eight encoder '
                                          'layers, output head, DDPM update and the next step\'s pack -- as one launch)' if dom == 'gemm_stack_tail' else
@@ -1216,16 +1242,16 @@ def main(argv=None):
             rec['dump_outputs'] = dumped
         if dist is not None:
             rec['process_group'] = {'backend': dist.get_backend(), 'world_size': dist.get_world_size(), 'forced': bool(args.force_dist)}
-        if world == 1 and (not args.no_cpu_baseline or args.config_cpu_baseline) and not prox:
+        if run['cpu_baseline'] and not prox:
             rec['cpu_baseline'] = cpu_baseline(batch=B)
-        if world == 1 and (not args.no_cpu_baseline or args.config_cpu_baseline) and prox:
+        if run['cpu_baseline'] and prox:
             try:
                 rec['cpu_baseline'] = cpu_baseline_config('prox', B)
             except Exception as e:
                 rec['cpu_baseline'] = {'error': f'{type(e).__name__}: {e}'}
-        if world == 1 and not prox and (args.with_accuracy or not args.no_cpu_baseline):
+        if run['accuracy']:
             rec['accuracy'] = accuracy_vs_reference(dev)
-        if world == 1 and not args.no_extras and not prox and not _PRODUCTS:
+        if run['extras']:
             torch.cuda.synchronize(dev)
             # safety copy of the headline on stderr before the child legs start (a slow or hung child can then cost the extras, never
             # the measurement); stdout still carries exactly ONE JSON line, printed below

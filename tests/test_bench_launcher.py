@@ -247,6 +247,61 @@ def _bench_module():
     return bench
 
 
+def test_a_plain_run_adds_no_legs_and_full_adds_them(monkeypatch):
+    """A plain run measures nothing after its timed passes; `--full` adds the attention figures, the CPU baseline, the accuracy
+    record and the children, `--no-cpu-baseline` / `--no-extras` thin it, and the children themselves run as full records."""
+    import subprocess as sp
+    import types
+    bench = _bench_module()
+    monkeypatch.setattr(bench, '_PRODUCTS', 0)
+
+    def ns(**kw):
+        base = dict(full=False, no_cpu_baseline=False, no_extras=False, with_accuracy=False, config_cpu_baseline=False,
+                    workload='posenet')
+        return types.SimpleNamespace(**{**base, **kw})
+    legs = {'attention', 'cpu_baseline', 'accuracy', 'extras'}
+    for wl in ('posenet', 'scheme', 'prox', 'egobody'):
+        for world in (1, 8):
+            assert set(bench.legs(ns(workload=wl), world)) == legs and not any(bench.legs(ns(workload=wl), world).values())
+    assert all(bench.legs(ns(full=True), 1).values())
+    assert bench.legs(ns(full=True), 8) == {'attention': True, 'cpu_baseline': False, 'accuracy': False, 'extras': False}
+    assert bench.legs(ns(full=True, workload='prox'), 1) == {'attention': True, 'cpu_baseline': True, 'accuracy': False, 'extras': False}
+    assert bench.legs(ns(full=True, no_cpu_baseline=True, no_extras=True), 1) == {'attention': True, 'cpu_baseline': False,
+                                                                                   'accuracy': False, 'extras': False}
+    # the explicit asks of the children hold in any run
+    assert bench.legs(ns(with_accuracy=True), 1)['accuracy'] and bench.legs(ns(config_cpu_baseline=True, workload='scheme'), 1)['cpu_baseline']
+    monkeypatch.setattr(bench, '_PRODUCTS', 3)
+    assert not bench.legs(ns(full=True), 1)['extras']
+    cmds = []
+    monkeypatch.setattr(sp, 'run', lambda cmd, **kw: cmds.append(cmd) or types.SimpleNamespace(returncode=1, stdout='', stderr=''))
+    assert 'error' in bench.run_child(['--workload', 'scheme'])
+    assert {'--full', '--no-extras', '--no-cpu-baseline'} <= set(cmds[0]) and cmds[0][-2:] == ['--workload', 'scheme']
+    monkeypatch.undo()
+    r = _run(['--gpus', '1', '--backend', 'gloo', '--full', '--steps', '1', '--warmup', '0', '--batch', '2'], {'ROHM_BENCH_SELFTEST': '1'})
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert _json_line(r.stdout)['steps'] == 1
+
+
+@pytest.mark.gpu
+def test_a_plain_run_prints_the_headline_only_and_full_adds_the_attention_figures():
+    """The real PoseNet path at B = 32 (one encoder-stack launch per step): a plain run carries no CPU baseline, accuracy record,
+    child measurements or attention figures of its own; `--full` (thinned to its GPU-only leg) measures the attention phase."""
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    recs = {}
+    for name, extra in (('plain', []), ('full', ['--full', '--no-cpu-baseline', '--no-extras'])):
+        r = subprocess.run([sys.executable, BENCH, '--steps', '1', '--warmup', '0', '--batch', '32', '--ddpm-steps', '10'] + extra,
+                           env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+        recs[name] = _json_line(r.stdout)
+    plain, full = recs['plain'], recs['full']
+    assert not {'cpu_baseline', 'accuracy', 'second_line', 'configs'} & set(plain)
+    assert plain['value'] > 0 and plain['roofline']['frac'] > 0 and plain['roofline']['attention_standalone'] is None
+    own_launch = {'achieved', 'frac', 'avg_launch_us', 'unit', 'peak'}          # attention timed as a launch of the timed passes
+    assert plain['roofline']['attention'] is None or set(plain['roofline']['attention']) == own_launch
+    assert full['roofline']['attention'] and 'error' not in full['roofline']['attention']
+    assert not {'cpu_baseline', 'accuracy', 'second_line', 'configs'} & set(full)
+
+
 def test_steps_sets_the_number_of_timed_passes():
     """`--steps K` times exactly K passes after exactly W untimed ones, and ms_per_step is the bracket over K passes / K."""
     import time
