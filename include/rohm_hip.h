@@ -303,6 +303,56 @@ int rohm_posenet_sample_loop(const rohm_posenet_t* h, float* x, const float* con
                              const float* coef, const float* noise, float* x0_last, float* x_in_last, int n_steps,
                              int B, int T, void* ws, size_t ws_bytes, rohm_stream_t stream);
 
+/* ------------------------------------------------------------------------- PoseNet training
+ * train/training_loop_posenet.py: the train-mode forward of PoseNet (model/posenet.py:75-96 with the five dropouts of
+ * model/heads.py:126-129 and nn.TransformerEncoderLayer) and its backward.  No handle: `w` holds device pointers to the LIVE
+ * parameters on every call (an optimiser step needs no rebuild).  Shapes: d_model 512, 4 heads, d_ff 1024, any n_layer >= 1,
+ * c_out + traj_dim == c_in, 1 <= B <= 16383, 1 <= T <= 143; anything else returns ROHM_ERR_UNSUPPORTED (rohm_last_error names
+ * the shape).  Exact fp32 (fp32 MFMA), no atomics (bitwise reproducible), no host synchronisation.
+ * Dropout (keep-scale 1 / (1 - p), 0 <= p < 1): element e of site s of layer l is kept iff a counter-based hash of (seed, 8 l + s, e)
+ * falls below (1 - p) 2^32.  Sites and the flat shapes their e indexes: 0 the PositionalEncoding dropout on the token sequence
+ * [B, T + 1, D] (layer 0 only), 1 attention probabilities [B, H, T + 1, T + 1], 2 dropout1 [B, T + 1, D], 3 FF inner after GELU
+ * [B, T + 1, F], 4 dropout2 [B, T + 1, D]; token 0 is the timestep token.  The backward regenerates the masks from (seed, p). */
+typedef struct {
+    float *in_proj_w, *in_proj_b, *out_proj_w, *out_proj_b, *lin1_w, *lin1_b, *lin2_w, *lin2_b;
+    float *norm1_w, *norm1_b, *norm2_w, *norm2_b;
+} rohm_posenet_layer_grads;
+
+typedef struct {       /* mirrors the weights struct: pe is a buffer and gets no gradient */
+    float *in_x_w, *in_x_b, *in_c_w, *in_c_b;
+    float *t_w0, *t_b0, *t_w2, *t_b2;
+    float *out_w, *out_b;
+    const rohm_posenet_layer_grads* layers; /* [n_layer], host array of device pointers */
+} rohm_posenet_grads;
+
+/* Bytes of the caller-owned `saved` buffer of rohm_posenet_train_forward (0 for an unsupported shape).  Per layer it keeps the
+ * layer input, qkv (q pre-scaled), the softmax probabilities, ctx, both pre-norm sums with their (mean, rstd), norm1's output, the
+ * FF1 pre-activation and the dropped GELU output; about 250 MB per layer at B = 64, T = 143. */
+size_t rohm_posenet_train_saved_bytes(int d_model, int n_head, int d_ff, int n_layer, int c_in, int c_out, int B, int T);
+/* Bytes of the `scratch` of rohm_posenet_train_backward (0 for an unsupported shape). */
+size_t rohm_posenet_train_scratch_bytes(int d_model, int n_head, int d_ff, int n_layer, int c_in, int c_out, int B, int T);
+/* PoseNet.forward in train mode (model/posenet.py:75-96): x_t, cond [B, c_in, 1, T], t int64 [B] -> out [B, c_in, 1, T] (channels
+ * < traj_dim copied from cond), and `saved` for the backward.  The timestep token is computed per sample from pe[t] (Linear -> SiLU
+ * -> Linear, model/heads.py:140-146).  saved: 16-byte aligned. */
+int rohm_posenet_train_forward(const rohm_posenet_weights* w, int d_model, int n_head, int d_ff, int n_layer, int c_in, int c_out,
+                               int traj_dim, const float* x_t, const float* cond, const int64_t* t, int B, int T, float dropout_p,
+                               unsigned long long seed, float* out, void* saved, size_t saved_bytes, rohm_stream_t stream);
+/* The backward of that forward for d_out = dL/d out [B, c_in, 1, T]: OVERWRITES every gradient in `grads` (108 state-dict
+ * tensors), and d_x_t / d_cond (nullable) with dL/dx_t, dL/dcond (d_cond includes the pass-through of the traj_dim channels).
+ * Same weights, inputs, dropout_p and seed as the forward that filled `saved` (read only: the call may be repeated). */
+int rohm_posenet_train_backward(const rohm_posenet_weights* w, int d_model, int n_head, int d_ff, int n_layer, int c_in, int c_out,
+                                int traj_dim, const float* x_t, const float* cond, int B, int T, float dropout_p,
+                                unsigned long long seed, const void* saved, size_t saved_bytes, const float* d_out,
+                                const rohm_posenet_grads* grads, float* d_x_t, float* d_cond, void* scratch, size_t scratch_bytes,
+                                rohm_stream_t stream);
+/* keep[e] = 1 if element e < n of dropout site `site` of layer `layer` is kept by the training forward with (seed, dropout_p). */
+int rohm_posenet_dropout_mask(unsigned long long seed, int layer, int site, float dropout_p, long long n, uint8_t* keep,
+                              rohm_stream_t stream);
+/* q_sample (gaussian_diffusion_posenet.py:192-210): out = sqrt_ac[t[b]] x0 + sqrt_1m_ac[t[b]] noise over row_len floats per
+ * sample; sqrt_ac / sqrt_1m_ac are device float tables of n_steps entries. */
+int rohm_q_sample(const float* x0, const float* noise, const float* sqrt_ac, const float* sqrt_1m_ac, const int64_t* t, int n_steps,
+                  int B, long long row_len, float* out, rohm_stream_t stream);
+
 /* ------------------------------------------------------------------------- TrajNet / TrajControl
  * model/trajnet.py:10-275 + model/heads.py:12-106: conv U-Net x0-predictor of the 13-channel trajectory,
  * optional ControlNet branch conditioned on PoseNet's 272-channel local pose. */

@@ -38,6 +38,15 @@ class PoseNetWeights(C.Structure):
                 ('layers', C.POINTER(LayerWeights))]
 
 
+class LayerGrads(C.Structure):
+    _fields_ = LayerWeights._fields_
+
+
+class PoseNetGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('in_x_w', 'in_x_b', 'in_c_w', 'in_c_b', 't_w0', 't_b0', 't_w2', 't_b2', 'out_w',
+                                          'out_b')] + [('layers', C.POINTER(LayerGrads))]
+
+
 class TensorRef(C.Structure):
     _fields_ = [('data', C.c_void_p), ('numel', C.c_size_t)]
 
@@ -108,6 +117,15 @@ SIGNATURES = {
     'rohm_posenet_sample_loop': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int64_p, c_float_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                            C.c_void_p]),
+    'rohm_posenet_train_saved_bytes': (C.c_size_t, [C.c_int] * 8),
+    'rohm_posenet_train_scratch_bytes': (C.c_size_t, [C.c_int] * 8),
+    'rohm_posenet_train_forward': (C.c_int, [C.POINTER(PoseNetWeights)] + [C.c_int] * 7 + [C.c_void_p] * 3 +
+                                   [C.c_int, C.c_int, C.c_float, C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rohm_posenet_train_backward': (C.c_int, [C.POINTER(PoseNetWeights)] + [C.c_int] * 7 + [C.c_void_p] * 2 +
+                                    [C.c_int, C.c_int, C.c_float, C.c_ulonglong, C.c_void_p, C.c_size_t, C.c_void_p,
+                                     C.POINTER(PoseNetGrads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rohm_posenet_dropout_mask': (C.c_int, [C.c_ulonglong, C.c_int, C.c_int, C.c_float, C.c_longlong, C.c_void_p, C.c_void_p]),
+    'rohm_q_sample': (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
     'rohm_trajnet_create': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(TrajNetWeights), C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_int, C.c_int]),
     'rohm_trajnet_destroy': (None, [C.c_void_p]),

@@ -488,8 +488,40 @@ class DDPMSampler:
                                  grad_type=grad_type, early_stop=early_stop)
         return None, out
 
-    def training_losses(self, *a, **k):
-        raise NotImplementedError('training is outside the inference hot path (SURVEY.md §8)')
+    def _scale_timesteps(self, t):
+        """gaussian_diffusion_posenet.py:305-308."""
+        return t.float() * (1000.0 / self.num_timesteps) if self.rescale_timesteps else t
+
+    def q_sample(self, x_start, t, noise=None):
+        """Sample from q(x_t | x_0) (gaussian_diffusion_posenet.py:192-210) with one device kernel (rohm_q_sample)."""
+        from .. import _lib
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        assert noise.shape == x_start.shape
+        _lib.require_hip(x_start, noise, t)
+        dev = x_start.device
+        key = ('q', str(dev))
+        if key not in self._tables_cache:
+            self._tables_cache[key] = (
+                torch.from_numpy(self.sqrt_alphas_cumprod.astype(np.float32)).to(dev).contiguous(),
+                torch.from_numpy(self.sqrt_one_minus_alphas_cumprod.astype(np.float32)).to(dev).contiguous())
+        sa, sb = self._tables_cache[key]
+        x_c = x_start.detach().to(torch.float32).contiguous()
+        n_c = noise.detach().to(device=dev, dtype=torch.float32).contiguous()
+        t_c = t.to(device=dev, dtype=torch.int64).contiguous()
+        B = x_c.shape[0]
+        if tuple(t_c.shape) != (B,):
+            raise ValueError(f't must be [{B}], got {tuple(t_c.shape)}')
+        out = torch.empty_like(x_c)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().rohm_q_sample(_lib.ptr(x_c), _lib.ptr(n_c), _lib.ptr(sa), _lib.ptr(sb), _lib.ptr(t_c),
+                                                self.num_timesteps, B, x_c[0].numel() if B else 0, _lib.ptr(out),
+                                                _lib.stream_ptr(dev)), 'rohm_q_sample')
+        return out
+
+    def training_losses(self, model, batch, t, noise=None, smplx_model=None, epoch=0):
+        raise NotImplementedError('only PoseNet training is native (GaussianDiffusionPoseNet.training_losses); the TrajNet / '
+                                  'TrajControl backward is not implemented')
 
 
 def _extract_into_tensor(arr, timesteps, broadcast_shape):

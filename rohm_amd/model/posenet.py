@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from .._lib import LayerWeights, PoseNetWeights, check, lib, ptr, stream_ptr
+from .._lib import LayerGrads, LayerWeights, PoseNetGrads, PoseNetWeights, check, lib, ptr, stream_ptr
 from .heads import InputProcess, OutputProcess, PositionalEncoding, TimestepEmbedder
 
 
@@ -145,6 +145,110 @@ class _NativePoseNet:
                 self.handle = None
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------------------------------------------------- training path
+_LAYER_KEYS = (('in_proj_w', 'self_attn.in_proj_weight'), ('in_proj_b', 'self_attn.in_proj_bias'),
+               ('out_proj_w', 'self_attn.out_proj.weight'), ('out_proj_b', 'self_attn.out_proj.bias'),
+               ('lin1_w', 'linear1.weight'), ('lin1_b', 'linear1.bias'), ('lin2_w', 'linear2.weight'), ('lin2_b', 'linear2.bias'),
+               ('norm1_w', 'norm1.weight'), ('norm1_b', 'norm1.bias'), ('norm2_w', 'norm2.weight'), ('norm2_b', 'norm2.bias'))
+_TOP_KEYS = (('in_x_w', 'input_process.poseEmbedding.weight'), ('in_x_b', 'input_process.poseEmbedding.bias'),
+             ('in_c_w', 'input_process_cond.poseEmbedding.weight'), ('in_c_b', 'input_process_cond.poseEmbedding.bias'),
+             ('t_w0', 'embed_timestep.time_embed.0.weight'), ('t_b0', 'embed_timestep.time_embed.0.bias'),
+             ('t_w2', 'embed_timestep.time_embed.2.weight'), ('t_b2', 'embed_timestep.time_embed.2.bias'),
+             ('out_w', 'output_process.poseFinal.weight'), ('out_b', 'output_process.poseFinal.bias'))
+
+
+def train_param_names(num_layers):
+    """State-dict names of the parameters the training path differentiates, in the order `_PoseNetTrain` takes them."""
+    return [k for _, k in _TOP_KEYS] + [f'seqTransEncoder.layers.{i}.{k}' for i in range(num_layers) for _, k in _LAYER_KEYS]
+
+
+def _fill(struct_cls, layer_cls, tensors, L):
+    """(top struct, layer array) of pointers to `tensors` (ordered as train_param_names)."""
+    top = struct_cls()
+    for (f, _), t in zip(_TOP_KEYS, tensors[:len(_TOP_KEYS)]):
+        setattr(top, f, C.c_void_p(t.data_ptr()))
+    layers = (layer_cls * L)()
+    rest = tensors[len(_TOP_KEYS):]
+    for i in range(L):
+        for j, (f, _) in enumerate(_LAYER_KEYS):
+            setattr(layers[i], f, C.c_void_p(rest[i * len(_LAYER_KEYS) + j].data_ptr()))
+    top.layers = layers
+    return top, layers
+
+
+def dropout_mask(seed, layer, site, shape, p, device):
+    """The keep mask (bool, `shape`) that the training forward draws with (seed, p) at dropout `site` of `layer`
+    (include/rohm_hip.h rohm_posenet_dropout_mask: 0 PositionalEncoding [B, T+1, D], 1 attention [B, H, T+1, T+1],
+    2 dropout1 [B, T+1, D], 3 FF inner [B, T+1, F], 4 dropout2 [B, T+1, D])."""
+    device = torch.device(device)
+    keep = torch.empty(tuple(shape), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        check(lib().rohm_posenet_dropout_mask(int(seed) & (2 ** 64 - 1), int(layer), int(site), float(p), keep.numel(), ptr(keep),
+                                              stream_ptr(device)), 'rohm_posenet_dropout_mask')
+    return keep.bool()
+
+
+class _PoseNetTrain(torch.autograd.Function):
+    """PoseNet.forward in train mode with dropout (rohm_posenet_train_forward) and its backward (rohm_posenet_train_backward).
+    Inputs: the module (dims), x_t, cond, timesteps, dropout p, seed, then the parameters in train_param_names order."""
+
+    @staticmethod
+    def forward(ctx, net, x_t, cond, t, p, seed, *params):
+        dev = x_t.device
+        B, _, _, T = x_t.shape
+        ws = [q.detach().to(dtype=torch.float32).contiguous() for q in params]
+        x_c = x_t.detach().to(torch.float32).contiguous()
+        c_c = cond.detach().to(torch.float32).contiguous()
+        t_c = t.to(torch.int64).contiguous()
+        pe = net.sequence_pos_encoder.pe[:, 0].detach().to(device=dev, dtype=torch.float32).contiguous()
+        w, layers = _fill(PoseNetWeights, LayerWeights, ws, net.num_layers)
+        w.pe, w.pe_len = C.c_void_p(pe.data_ptr()), pe.shape[0]
+        dims = (net.latent_dim, net.num_heads, net.ff_size, net.num_layers, net.input_feats, net.dataset_pose_feat_dim)
+        traj = net.input_feats - net.dataset_pose_feat_dim
+        nbytes = lib().rohm_posenet_train_saved_bytes(*dims, B, T)
+        if nbytes == 0:
+            m = lib().rohm_last_error()
+            raise _lib.RohmHipError(f'PoseNet training path: {m.decode() if m else "unsupported shape"} (x_t {tuple(x_t.shape)})')
+        saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty_like(x_c)
+        with torch.cuda.device(dev):
+            check(lib().rohm_posenet_train_forward(C.byref(w), *dims, traj, ptr(x_c), ptr(c_c), ptr(t_c), B, T, float(p), seed,
+                                                   ptr(out), ptr(saved), nbytes, stream_ptr(dev)), 'rohm_posenet_train_forward')
+        ctx.net_dims, ctx.traj, ctx.BT, ctx.p, ctx.seed = dims, traj, (B, T), float(p), seed
+        ctx.keep = (w, layers, pe, saved)
+        ctx.save_for_backward(x_c, c_c, *ws)
+        ctx.meta = [(q.shape, q.dtype) for q in params]
+        ctx.in_dtypes = (x_t.dtype, cond.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        x_c, c_c, *ws = ctx.saved_tensors
+        w, _, _, saved = ctx.keep
+        dev = x_c.device
+        B, T = ctx.BT
+        dims = ctx.net_dims
+        d_out = d_out.to(torch.float32).contiguous()
+        sizes = [q.numel() for q in ws]
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        views = [v.view(q.shape) for v, q in zip(flat.split(sizes), ws)]
+        g, glayers = _fill(PoseNetGrads, LayerGrads, views, dims[3])
+        d_x = torch.empty_like(x_c) if ctx.needs_input_grad[1] else None
+        d_c = torch.empty_like(c_c) if ctx.needs_input_grad[2] else None
+        nscr = lib().rohm_posenet_train_scratch_bytes(*dims, B, T)
+        scratch = torch.empty(nscr, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(lib().rohm_posenet_train_backward(C.byref(w), *dims, ctx.traj, ptr(x_c), ptr(c_c), B, T, ctx.p, ctx.seed,
+                                                    ptr(saved), saved.numel(), ptr(d_out), C.byref(g), ptr(d_x), ptr(d_c),
+                                                    ptr(scratch), nscr, stream_ptr(dev)), 'rohm_posenet_train_backward')
+        grads = [v if dt == torch.float32 else v.to(dt) for v, (_, dt) in zip(views, ctx.meta)]
+        if d_x is not None and ctx.in_dtypes[0] != torch.float32:
+            d_x = d_x.to(ctx.in_dtypes[0])
+        if d_c is not None and ctx.in_dtypes[1] != torch.float32:
+            d_c = d_c.to(ctx.in_dtypes[1])
+        return (None, d_x, d_c, None, None, None, *grads)
 
 
 class PoseNet(nn.Module):
@@ -287,7 +391,6 @@ class PoseNet(nn.Module):
         (model/posenet.py:75-96)."""
         x_t, cond = batch['x_t'], batch['cond']
         _lib.require_hip(x_t, cond, timesteps)
-        nat = self.native(x_t.device)
         B, Cc, nf, T = x_t.shape
         if Cc != self.input_feats or nf != 1:
             raise ValueError(f'x_t must be [B, {self.input_feats}, 1, T]; got {tuple(x_t.shape)}')
@@ -295,6 +398,11 @@ class PoseNet(nn.Module):
             raise ValueError(f'cond must have the shape of x_t {tuple(x_t.shape)}, got {tuple(cond.shape)}')
         if tuple(timesteps.shape) != (B,):
             raise ValueError(f'timesteps must be [{B}], got {tuple(timesteps.shape)}')
+        if self.training and torch.is_grad_enabled() and B > 0 and T > 0:
+            params = self.train_parameters()
+            if x_t.requires_grad or cond.requires_grad or any(q.requires_grad for q in params):
+                return self._forward_train(x_t, cond, timesteps, params)
+        nat = self.native(x_t.device)
         x_c = x_t.detach().to(torch.float32).contiguous()
         c_c = cond.detach().to(torch.float32).contiguous()
         t_c = timesteps.to(torch.int64).contiguous()
@@ -305,6 +413,20 @@ class PoseNet(nn.Module):
         check(lib().rohm_posenet_forward(nat.handle, ptr(x_c), ptr(c_c), ptr(t_c), ptr(out), B, T, ptr(ws),
                                          ws.numel(), stream_ptr(x_c.device)), 'rohm_posenet_forward')
         return out
+
+    # ------------------------------------------------------------------ training (train mode with autograd)
+    def train_parameters(self):
+        """The parameters of train_param_names(num_layers), in that order."""
+        named = dict(self.named_parameters())
+        return [named[k] for k in train_param_names(self.num_layers)]
+
+    def _forward_train(self, x_t, cond, timesteps, params):
+        """Train-mode forward through `_PoseNetTrain`: dropout self.dropout at the reference's five sites, the seed drawn from
+        torch's CPU generator (torch.manual_seed reproduces a step); kept in `last_dropout_seed` for diagnostics."""
+        p = float(self.dropout)
+        seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64).item()) if p > 0 else 0
+        self.last_dropout_seed = seed
+        return _PoseNetTrain.apply(self, x_t, cond, timesteps, p, seed, *params)
 
     # ------------------------------------------------------------------ fused sampling loop
     def sample_loop_native(self, x, cond, t_model, coef, noise, want_x0_last=False, batch=None, x_in_last=None):
