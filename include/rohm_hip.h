@@ -15,6 +15,9 @@
  *     forward/step call: scratch comes from the caller's workspace
  *     (*_workspace_bytes).  Weights are copied and re-laid-out at *_create time, so
  *     the caller may free its copies afterwards.
+ *     The training entry points (rohm_posenet_train_*, rohm_trajnet_train_*) have no handle: they read the
+ *     caller's LIVE parameters in the reference's layouts on every call and keep their state in caller-owned
+ *     `saved` / `scratch` buffers (*_saved_bytes, *_scratch_bytes).
  *   - every launch goes on the caller-supplied hipStream_t (passed as void*);
  *     no hidden device synchronisation in forward / step / loop calls.  Set-up calls say so where they
  *     synchronise: *_create, rohm_exchange_probe, rohm_posenet_set_exchange(h, 1), the status read
@@ -399,6 +402,37 @@ int rohm_trajnet_sample_loop(const rohm_trajnet_t* h, float* x, const float* con
  * ROHM_TRAJ_RESIDENT=0; when it runs, rohm_trajnet_sample_loop waits for the stream once at its end to read the exchange's error word, and
  * a wait that expired hands the call back to form 0 with x restored).  No counterpart in the reference. */
 int rohm_trajnet_loop_mode(void);
+
+/* ------------------------------------------------------------------------- TrajNet / TrajControl training
+ * train/training_loop_trajnet.py: the train-mode forward of TrajNet (model/trajnet.py:177-275; no dropout, GroupNorm without
+ * running statistics: the function of rohm_trajnet_forward) and the backward of the whole conv U-Net with its ControlNet branch.
+ * No handle: `w` lists device pointers to the LIVE parameters in the reference's layouts (Conv1d [C_out, C_in, k],
+ * ConvTranspose1d [C_in, C_out, k]) in state_dict order, as for rohm_trajnet_create; gradients are written in those layouts.
+ * Shapes: mid_dim 512, time_dim 32, 1 <= c_traj <= 32, c_ctrl <= 320, 1 <= B <= 16383, T a multiple of 16 with T <= 512 (the
+ * GroupNorm group limit of the inference forward); anything else returns ROHM_ERR_UNSUPPORTED (rohm_last_error names the shape).
+ * Exact fp32 (fp32 MFMA), no atomics (bitwise reproducible), no host synchronisation. */
+/* Bytes of the caller-owned `saved` buffer of rohm_trajnet_train_forward (0 for an unsupported shape): the zero-haloed inputs, per
+ * Conv1dBlock the conv output and the group statistics, per residual block its block-0 activation and output, the concat buffers. */
+size_t rohm_trajnet_train_saved_bytes(int mid_dim, int time_dim, int c_traj, int c_ctrl, int trajcontrol, int B, int T);
+/* Bytes of the `scratch` of rohm_trajnet_train_backward (0 for an unsupported shape). */
+size_t rohm_trajnet_train_scratch_bytes(int mid_dim, int time_dim, int c_traj, int c_ctrl, int trajcontrol, int B, int T);
+/* TrajNet.forward in train mode: x_t, cond [B, T, c_traj], control_cond [B, T, c_ctrl] (NULL without TrajControl), t int64 [B]
+ * -> out [B, T, c_traj], and `saved` (16-byte aligned) for the backward. */
+int rohm_trajnet_train_forward(const rohm_trajnet_weights* w, int mid_dim, int time_dim, int c_traj, int c_ctrl, int trajcontrol,
+                               const float* x_t, const float* cond, const float* control_cond, const int64_t* t, int B, int T,
+                               float* out, void* saved, size_t saved_bytes, rohm_stream_t stream);
+/* The backward of that forward for d_out = dL/d out [B, T, c_traj].  grads: host array of w->n_tensors device pointers, one per
+ * parameter in the order of `w`; a NULL entry means the parameter is frozen: its weight-gradient product is not launched, and data
+ * gradients are propagated only as far as a non-NULL entry or a wanted input gradient lies upstream.  Every non-NULL gradient
+ * is OVERWRITTEN.  cond_downsample4 is never called by the reference and must be NULL.  d_x_t / d_cond / d_control_cond (each
+ * nullable) receive dL/dx_t, dL/dcond, dL/dcontrol_cond.  `saved` is read only: the call may be repeated. */
+int rohm_trajnet_train_backward(const rohm_trajnet_weights* w, int mid_dim, int time_dim, int c_traj, int c_ctrl, int trajcontrol,
+                                int B, int T, const void* saved, size_t saved_bytes, const float* d_out, float* const* grads,
+                                float* d_x_t, float* d_cond, float* d_control_cond, void* scratch, size_t scratch_bytes,
+                                rohm_stream_t stream);
+/* GEMM launches (conv, data-gradient and weight-gradient products) of the process's last rohm_trajnet_train_backward:
+ * a frozen backbone launches fewer than an all-trainable step. */
+int rohm_trajnet_train_last_gemms(void);
 
 /* ------------------------------------------------------------------------- SMPL-X + guidance
  * Joints-only SMPL-X (third-party smplx==0.1.28 `SMPLX.forward` / `lbs`, called from

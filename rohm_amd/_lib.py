@@ -137,6 +137,14 @@ SIGNATURES = {
     'rohm_trajnet_sample_loop': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int64_p, c_float_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                            C.c_size_t, C.c_void_p]),
+    'rohm_trajnet_train_saved_bytes': (C.c_size_t, [C.c_int] * 7),
+    'rohm_trajnet_train_scratch_bytes': (C.c_size_t, [C.c_int] * 7),
+    'rohm_trajnet_train_forward': (C.c_int, [C.POINTER(TrajNetWeights)] + [C.c_int] * 5 + [C.c_void_p] * 4 +
+                                   [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rohm_trajnet_train_backward': (C.c_int, [C.POINTER(TrajNetWeights)] + [C.c_int] * 7 +
+                                    [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rohm_trajnet_train_last_gemms': (C.c_int, []),
     'rohm_smplx_create': (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_int, C.c_int, C.c_int]),
     'rohm_smplx_destroy': (None, [C.c_void_p]),

@@ -21,9 +21,10 @@
 namespace rohm {
 namespace {
 
+#include "train_reduce.h"
+
 constexpr int kD = 512, kH = 4, kF = 1024, kDh = 128, kMaxS = 144;
 constexpr int kRowsPerSplit = 576;      // token rows per weight-gradient slice (4 clips of 144)
-constexpr int kColRows = 256;           // rows per column-sum chunk
 
 // ---------------------------------------------------------------------------------------------------------------- dropout
 __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
@@ -352,34 +353,6 @@ __global__ void traj_copy_kernel(const float* __restrict__ src, float* __restric
     dst[o] = add ? dst[o] + src[o] : src[o];
 }
 
-// Column sums, first pass: part[chunk][n] = sum over rows r of the chunk of X(r, n), X(r, n) = X[(r / inner) outer_stride +
-// (r % inner) inner_stride + n col_stride]; 64 columns x 4 row phases per workgroup, the phases added in a fixed order.
-__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ X, long long outer_stride, int inner,
-                                                     long long inner_stride, long long col_stride, int rows, int N,
-                                                     float* __restrict__ part) {
-    __shared__ float red[4][64];
-    const int c = threadIdx.x & 63, ph = threadIdx.x >> 6;
-    const int n = blockIdx.x * 64 + c;
-    const int r0 = blockIdx.y * kColRows;
-    float s = 0.f;
-    if (n < N)
-        for (int r = r0 + ph; r < r0 + kColRows && r < rows; r += 4)
-            s += X[(long long)(r / inner) * outer_stride + (long long)(r % inner) * inner_stride + n * col_stride];
-    red[ph][c] = s;
-    __syncthreads();
-    if (ph == 0 && n < N) part[(long long)blockIdx.y * N + n] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
-}
-
-// out[i] = sum_s part[s][i], slabs added in index order; out2 (optional) receives the same values
-__global__ void reduce_slabs_kernel(const float* __restrict__ part, int S, long long n, float* __restrict__ out, float* __restrict__ out2) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float s = part[i];
-    for (int k = 1; k < S; ++k) s += part[(long long)k * n + i];
-    out[i] = s;
-    if (out2) out2[i] = s;
-}
-
 __global__ void q_sample_kernel(const float* __restrict__ x0, const float* __restrict__ noise, const float* __restrict__ sa,
                                 const float* __restrict__ sb, const int64_t* __restrict__ t, int n_steps, int B, long long row,
                                 float* __restrict__ out) {
@@ -391,8 +364,6 @@ __global__ void q_sample_kernel(const float* __restrict__ x0, const float* __res
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-inline unsigned blocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
-
 TG tg_plain() {
     TG p;
     memset(&p, 0, sizeof(p));
@@ -497,17 +468,6 @@ int check_dims(int d_model, int n_head, int d_ff, int n_layer, int c_in, int c_o
     Dims& d = *out;
     d.D = d_model; d.H = n_head; d.F = d_ff; d.L = n_layer; d.c_in = c_in; d.c_out = c_out; d.traj = traj; d.B = B; d.T = T;
     d.S = T + 1; d.M = B * d.S;
-    return ROHM_OK;
-}
-
-int colsum(const float* X, long long outer_stride, int inner, long long inner_stride, long long col_stride, int rows, int N,
-           float* out, float* out2, float* part, hipStream_t s) {
-    const int chunks = (rows + kColRows - 1) / kColRows;
-    hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64, chunks), dim3(256), 0, s, X, outer_stride, inner, inner_stride, col_stride,
-                       rows, N, part);
-    ROHM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(reduce_slabs_kernel, dim3(blocks(N, 256)), dim3(256), 0, s, part, chunks, (long long)N, out, out2);
-    ROHM_LAUNCH_CHECK();
     return ROHM_OK;
 }
 

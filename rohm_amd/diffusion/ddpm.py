@@ -520,8 +520,10 @@ class DDPMSampler:
         return out
 
     def training_losses(self, model, batch, t, noise=None, smplx_model=None, epoch=0):
-        raise NotImplementedError('only PoseNet training is native (GaussianDiffusionPoseNet.training_losses); the TrajNet / '
-                                  'TrajControl backward is not implemented')
+        net = getattr(model, 'model', model)
+        raise NotImplementedError('only PoseNet training is native on the generic sampler (GaussianDiffusionPoseNet.training_losses); '
+                                  'TrajNet / TrajControl train through GaussianDiffusionTrajNet.training_losses with a rohm_amd '
+                                  f'TrajNet, got {type(net).__name__}')
 
 
 def _extract_into_tensor(arr, timesteps, broadcast_shape):

@@ -127,6 +127,79 @@ class _NativeTrajNet:
             pass
 
 
+class _TrajNetTrain(torch.autograd.Function):
+    """TrajNet.forward in train mode (rohm_trajnet_train_forward) and its backward (rohm_trajnet_train_backward).
+    Inputs: the module (dims), x_t, cond, control_cond or None, timesteps, then the parameters in weight_order() order.  A
+    parameter with requires_grad=False gets a null gradient pointer (its weight-gradient product is not launched) and None."""
+
+    @staticmethod
+    def _table(ws):
+        refs = (TensorRef * len(ws))()
+        for r, q in zip(refs, ws):
+            r.data, r.numel = q.data_ptr(), q.numel()
+        return TrajNetWeights(refs, len(ws)), refs
+
+    @staticmethod
+    def forward(ctx, net, x_t, cond, ctrl, t, *params):
+        dev = x_t.device
+        B, T, _ = x_t.shape
+        ws = [q.detach().to(dtype=torch.float32).contiguous() for q in params]
+        x_c = x_t.detach().to(torch.float32).contiguous()
+        c_c = cond.detach().to(torch.float32).contiguous()
+        k_c = None if ctrl is None else ctrl.detach().to(torch.float32).contiguous()
+        t_c = t.to(device=dev, dtype=torch.int64).contiguous()
+        dims = (net.mid_dim, net.time_dim, net.traj_feat_dim, net.control_cond_dim, int(net.trajcontrol))
+        nbytes = lib().rohm_trajnet_train_saved_bytes(*dims, B, T)
+        if nbytes == 0:
+            m = lib().rohm_last_error()
+            raise _lib.RohmHipError(f'TrajNet training path: {m.decode() if m else "unsupported shape"} (x_t {tuple(x_t.shape)}, T={T})')
+        w, refs = _TrajNetTrain._table(ws)
+        saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty_like(x_c)
+        with torch.cuda.device(dev):
+            check(lib().rohm_trajnet_train_forward(C.byref(w), *dims, ptr(x_c), ptr(c_c), ptr(k_c), ptr(t_c), B, T, ptr(out),
+                                                   ptr(saved), nbytes, stream_ptr(dev)), 'rohm_trajnet_train_forward')
+        ctx.dims, ctx.BT, ctx.saved = dims, (B, T), saved
+        ctx.names = weight_order(net.mid_dim, net.traj_feat_dim, net.trajcontrol)
+        ctx.save_for_backward(*ws)
+        ctx.meta = [q.dtype for q in params]
+        ctx.in_meta = (x_t.dtype, cond.dtype, None if ctrl is None else (ctrl.dtype, tuple(ctrl.shape)), tuple(x_t.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        ws = ctx.saved_tensors
+        saved, dims = ctx.saved, ctx.dims
+        dev = saved.device
+        B, T = ctx.BT
+        d_out = d_out.to(torch.float32).contiguous()
+        # cond_downsample4 is built but never called (model/trajnet.py:174): like the reference's autograd it gets no gradient
+        want = [bool(n) and not k.startswith('cond_downsample4.') for n, k in zip(ctx.needs_input_grad[5:], ctx.names)]
+        sizes = [q.numel() if n else 0 for q, n in zip(ws, want)]
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        views = [v.view(q.shape) if n else None for v, q, n in zip(flat.split(sizes), ws, want)]
+        gptr = (C.c_void_p * len(ws))(*[None if v is None else v.data_ptr() for v in views])
+        x_dt, c_dt, k_meta, x_shape = ctx.in_meta
+        d_x = torch.empty(x_shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        d_c = torch.empty(x_shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+        d_k = torch.empty(k_meta[1], dtype=torch.float32, device=dev) if k_meta is not None and ctx.needs_input_grad[3] else None
+        w, refs = _TrajNetTrain._table(ws)
+        nscr = lib().rohm_trajnet_train_scratch_bytes(*dims, B, T)
+        scratch = torch.empty(nscr, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(lib().rohm_trajnet_train_backward(C.byref(w), *dims, B, T, ptr(saved), saved.numel(), ptr(d_out), gptr, ptr(d_x),
+                                                    ptr(d_c), ptr(d_k), ptr(scratch), nscr, stream_ptr(dev)),
+                  'rohm_trajnet_train_backward')
+        grads = [None if v is None else (v if dt == torch.float32 else v.to(dt)) for v, dt in zip(views, ctx.meta)]
+        if d_x is not None and x_dt != torch.float32:
+            d_x = d_x.to(x_dt)
+        if d_c is not None and c_dt != torch.float32:
+            d_c = d_c.to(c_dt)
+        if d_k is not None and k_meta[0] != torch.float32:
+            d_k = d_k.to(k_meta[0])
+        return (None, d_x, d_c, d_k, None, *grads)
+
+
 class TrajNet(nn.Module):
     """Drop-in for `model.trajnet.TrajNet` (model/trajnet.py:80-174)."""
 
@@ -216,7 +289,14 @@ class TrajNet(nn.Module):
         return ctrl.detach().float().contiguous()
 
     def forward(self, batch, time):
-        """model/trajnet.py:177-275."""
+        """model/trajnet.py:177-275.  In train mode with grad enabled, when an input or a parameter requires grad, the call runs
+        the differentiable native path (_TrajNetTrain: live parameters, HIP backward); every other call is the inference forward.
+        Only this module's own `training` flag is read (the reference calls .eval() on frozen sub-modules of a training module)."""
+        if self.training and torch.is_grad_enabled() and batch['x_t'].shape[0] > 0:
+            params = self.train_parameters()
+            ins = (batch['x_t'], batch['cond'], batch.get('control_cond') if self.trajcontrol else None)
+            if any(q.requires_grad for q in params) or any(q is not None and q.requires_grad for q in ins):
+                return self._forward_train(batch, time, params)
         x, c, ctrl, B, T = self._inputs(batch)
         nat = self.native(x.device)
         t = time.to(torch.int64).contiguous()
@@ -227,6 +307,23 @@ class TrajNet(nn.Module):
         check(lib().rohm_trajnet_forward(nat.handle, ptr(x), ptr(c), ptr(ctrl), ptr(t), ptr(out), B, T, ptr(ws),
                                          ws.numel(), stream_ptr(x.device)), 'rohm_trajnet_forward')
         return out
+
+    # ------------------------------------------------------------------ training (train mode with autograd)
+    def train_parameters(self):
+        """The parameters of weight_order(), in that order."""
+        named = dict(self.named_parameters())
+        return [named[k] for k in weight_order(self.mid_dim, self.traj_feat_dim, self.trajcontrol)]
+
+    def _forward_train(self, batch, time, params):
+        x_t, cond = batch['x_t'], batch['cond']
+        _lib.require_hip(x_t, cond)
+        if x_t.dim() != 3 or x_t.shape[2] != self.traj_feat_dim:
+            raise ValueError(f'x_t must be [B, T, {self.traj_feat_dim}], got {tuple(x_t.shape)}')
+        self._check_cond(x_t, cond, batch)
+        ctrl = batch['control_cond'] if self.trajcontrol else None
+        if tuple(time.shape) != (x_t.shape[0],):
+            raise ValueError(f'timesteps must be [{x_t.shape[0]}], got {tuple(time.shape)}')
+        return _TrajNetTrain.apply(self, x_t, cond, ctrl, time, *params)
 
     def sample_loop_native(self, x, cond, t_model, coef, noise, want_x0_last=False, batch=None, x_in_last=None):
         """`n` DDPM steps on the device (rohm_trajnet_sample_loop); x [B, T, 13] is updated in place.  `x_in_last` (optional,
@@ -261,6 +358,6 @@ class TrajNet(nn.Module):
         return x0_last
 
     def compute_losses_with_smpl(self, batch, model_output, smplx_model=None):
-        """Evaluation loss report (model/trajnet.py:277-400), forward only."""
+        """The loss report of model/trajnet.py:277-400; differentiable with respect to model_output (training_losses)."""
         from .eval_losses import trajnet_losses
         return trajnet_losses(self, batch, model_output, smplx_model)
