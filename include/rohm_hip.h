@@ -579,6 +579,51 @@ int rohm_scene_metrics(const float* joints_rec, const float* trans_scene2cano, c
                        const float* joints_gt, int T_gt, const float* mask_vis, float* joints_scene, int B, int T,
                        double* out, rohm_stream_t stream);
 
+/* Depth rendering and PROX joint-occlusion masks (csrc/raster.hip): utils/get_occlusion_mask.py without pyrender, trimesh or
+ * OpenCV.  One coverage rule everywhere: a pinhole camera in OpenCV axes (x right, y down, z forward: pyrender's
+ * IntrinsicsCamera under the script's diag(1, -1, -1, 1) pose, get_occlusion_mask.py:64-69); pixel (x, y) samples the ray
+ * through u = x + 0.5, v = y + 0.5; its depth is the smallest camera-space z, znear <= z <= zfar, at which that ray meets
+ * any triangle, 0 where it meets none (pyrender's znear / zfar defaults are 0.05 / 100).  Meshes are two-sided unless
+ * cull_backfaces != 0, which drops triangles that run clockwise as seen from the camera (OpenGL's default under pyrender;
+ * scene scans are open surfaces, so the two differ where a surface is seen from behind).  Triangles may cross z = 0 or lie
+ * behind the camera: the test uses homogeneous edge functions in fp64 and needs no clipper; depths are fp32.
+ *
+ * rohm_depth_render replaces the two r.render calls (get_occlusion_mask.py:82-88 for the scene, :122-129 per body):
+ * verts [n_mesh, V, 3] fp32 and faces [F, 3] int32 (one face list for all meshes) on the device; transform: 16 floats in
+ * HOST memory, a row-major 4 x 4 rigid transform applied to every vertex on the device (the script's
+ * apply_transform(inv(cam2world)), :77-78), or NULL for vertices already in camera space.  depth [n_mesh, H, W] fp32.
+ * Faces with an index outside [0, V) are skipped.  ws: rohm_depth_workspace_bytes(n_mesh, F, W, H) bytes, 256-byte
+ * aligned (about 108 bytes per triangle); nothing is allocated, the stream is the caller's and is never synchronised.
+ * Depths are merged with an unsigned min on the float's bit pattern: the image is bitwise reproducible.
+ *
+ * rohm_depth_probe is the same rule at listed pixels only: pixels [n_mesh, P, 2] int32 (x, y) in, depth [n_mesh, P] out;
+ * a pixel outside the image yields 0.  It agrees bit for bit with the rendered image at those pixels and is what the
+ * mask needs (25 pixels of every frame's body, :138-143) without one 8 MB image per frame.  No workspace. */
+size_t rohm_depth_workspace_bytes(int n_mesh, int F, int W, int H);
+int rohm_depth_render(const float* verts, const int* faces, int n_mesh, int V, int F, const float* transform, double fx,
+                      double fy, double cx, double cy, int W, int H, double znear, double zfar, int cull_backfaces,
+                      float* depth, void* ws, size_t ws_bytes, rohm_stream_t stream);
+int rohm_depth_probe(const float* verts, const int* faces, int n_mesh, int V, int F, const float* transform, double fx,
+                     double fy, double cx, double cy, int W, int H, double znear, double zfar, int cull_backfaces,
+                     const int* pixels, int P, float* depth, rohm_stream_t stream);
+
+/* cv2.projectPoints with zero rotation and translation (get_occlusion_mask.py:43-46, :133-136): joints [N, J, 3] fp32 in
+ * camera space on the device; camera_mtx (9 doubles, row-major 3 x 3) and dist (k1, k2, p1, p2, k3) in HOST memory.
+ * OpenCV's published model in fp64: x' = X / Z, y' = Y / Z (Z == 0 divides by 1), r2 = x'^2 + y'^2,
+ * x" = x' (1 + k1 r2 + k2 r2^2 + k3 r2^3) + 2 p1 x' y' + p2 (r2 + 2 x'^2), y" = y' (...) + p1 (r2 + 2 y'^2) + 2 p2 x' y',
+ * u = fx x" + cx, v = fy y" + cy; then astype(int), i.e. truncation toward zero.  pixels [N, J, 2] int32 (x, y), the
+ * input of the probe; a value beyond the int range becomes INT_MIN, outside every image. */
+int rohm_project_pixels(const float* joints, const double* camera_mtx, const double* dist, int N, int J, int* pixels,
+                        rohm_stream_t stream);
+
+/* The mask decision, get_occlusion_mask.py:138-143: projects as rohm_project_pixels does, then a joint is occluded
+ * (mask 0) iff its pixel lies inside the W x H image, scene_depth there is not 0 and body_depth - scene_depth > thr
+ * (a float32 difference, as on the script's float32 images; thr is 0.1 there); every other joint is visible (mask 1).
+ * scene_depth [H, W] from the renderer, body_depth [N, J] from the probe at the projected pixels, mask [N, J] fp32. */
+int rohm_joint_occlusion_mask(const float* joints, const double* camera_mtx, const double* dist, const float* scene_depth,
+                              int W, int H, const float* body_depth, float thr, int N, int J, float* mask,
+                              rohm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('ROHM_HIP_LIB') or os.path.join(_HERE, 'librohm_hip.so
 
 c_float_p = C.POINTER(C.c_float)
 c_int64_p = C.POINTER(C.c_int64)
+c_double_p = C.POINTER(C.c_double)
 
 
 class RohmHipError(RuntimeError):
@@ -177,6 +178,14 @@ SIGNATURES = {
     'rohm_traj_rederive': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong] +
                            [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong,
                                                C.c_void_p]),
+    'rohm_depth_workspace_bytes': (C.c_size_t, [C.c_int] * 4),
+    'rohm_depth_render': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_float_p] + [C.c_double] * 4 +
+                          [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rohm_depth_probe': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_float_p] + [C.c_double] * 4 +
+                         [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'rohm_project_pixels': (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'rohm_joint_occlusion_mask': (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 
