@@ -624,6 +624,71 @@ int rohm_joint_occlusion_mask(const float* joints, const double* camera_mtx, con
                               int W, int H, const float* body_depth, float thr, int N, int J, float* mask,
                               rohm_stream_t stream);
 
+/* Evaluation pictures (csrc/shade.hip): the render path of eval_amass_full.py:277-395, eval_prox_egobody.py:373-451 and
+ * utils/render_util.py without pyrender, trimesh, an OpenGL context or PIL.  Device pointers, the caller's stream, never
+ * synchronised, nothing allocated.
+ *
+ * rohm_vertex_normals: smooth normals in gather form (no float atomics, hence the same bits on every call).  verts
+ * [n_mesh, V, 3] fp32, faces [F, 3] int32 and the vertex -> face adjacency in CSR form, offsets [V + 1] and face_ids [3F]
+ * int32 (the faces of vertex v are face_ids[offsets[v] .. offsets[v + 1])).  Thread (mesh, vertex) sums the un-normalised
+ * (p1 - p0) x (p2 - p0) of its faces in list order, which weights by area, and normalises, in fp32.  A vertex with no
+ * face, or with a zero sum, gets (0, 0, 0).  normals [n_mesh, V, 3] fp32.
+ *
+ * rohm_color_render: mesh, camera, transform and workspace arguments are those of rohm_depth_render (the workspace size
+ * comes from rohm_color_workspace_bytes).  normals [n_mesh, V, 3] fp32 in the vertices' coordinates, or NULL for flat
+ * shading with the face normal; colors uint8 [n_mesh, V, 4] (colors_per_mesh != 0) or [1, V, 4] (== 0) RGBA; outputs rgba
+ * uint8 [n_mesh, H, W, 4] and, when not NULL, depth fp32 [n_mesh, H, W] and face_id int32 [n_mesh, H, W] (-1: nothing hit).
+ * The rule:
+ *   - Coverage and depth are exactly the rule above; the depth output equals rohm_depth_render's image bit for bit.
+ *   - Winner of a pixel: the smallest fp32 depth pattern; among equal patterns the smallest face index.  The tile's LDS
+ *     z-buffer holds a 64-bit key (depth bits << 32) | face per pixel, merged with an unsigned 64-bit atomic min:
+ *     order-independent, hence bitwise reproducible.
+ *   - Resolve, once per covered pixel after the tile's triangles are merged.  Weights l_i = e_i / (e_0 + e_1 + e_2) from
+ *     the winner's edge functions in fp64: the perspective-correct barycentrics of the hit point.  Normal
+ *     n = normalise(sum l_i n_i), the n_i taken to camera space by the call's rotation; the normalised face normal
+ *     (p1 - p0) x (p2 - p0) when normals is NULL.  Without the cull flag a normal facing away from the eye (n . d > 0, d the
+ *     pixel's ray) is negated.  One directional light along the viewing axis (the reference places its light at the camera
+ *     pose): lambert = max(0, -n_z) in the OpenCV axes.  Colour c_k = sum l_i C_ik / 255, alpha a = sum l_i A_i / 255;
+ *     out_k = floor(255 min(1, c_k (ambient + diffuse lambert)) + 0.5), out_a = floor(255 a + 0.5); a missed pixel is
+ *     (0, 0, 0, 0).  Shading arithmetic is fp32.
+ *   - The reference's scene has ambient 0.3; its intensity-3 light on a non-metallic material gives diffuse 3 / pi.  No
+ *     specular term, no sRGB curve, and nothing behind a translucent surface is blended: the nearest surface is drawn and
+ *     its alpha written.  These are stated differences from pyrender; nothing is pinned to it, as for depth.
+ *
+ * rohm_skeleton_mesh: create_pyrender_skel's geometry (render_util.py:119-158), batched.  joints [N, J, 3]; a unit sphere
+ * template [Vs, 3] and a unit cylinder template [Vc, 3] (axis z, from 0 to 1); limbs [L, 2] int32 joint pairs; hide
+ * [N, J + L] bytes (or NULL).  verts [N, J Vs + L Vc, 3]: sphere j is joint j + r_joint x template; cylinder l runs from
+ * p1 = joint limbs[l][0] to p2 = joint limbs[l][1] in the frame a = (p2 - p1) / |p2 - p1|, u = normalise(a x e) with e the
+ * coordinate axis of smallest |a . e| (ties: the lowest index), w = a x u: p1 + r_limb (x u + y w) + z |p2 - p1| a.  A
+ * hidden primitive, or a limb of zero length, collapses onto its first joint; the renderer drops zero-area triangles, so
+ * one face list serves the whole batch.
+ *
+ * The scripts' image arithmetic on uint8 images, elementwise and bit for bit:
+ *   rohm_image_requantize  render_img: every RGBA channel x -> float32(x) / 255, alpha times `alpha`, then (x * 255)
+ *                          truncated to uint8 (the colour channels take the same round trip).
+ *   rohm_image_paste       Image.paste(src, (0, 0), src) in place on an RGB or RGBA destination: with a = src alpha,
+ *                          t = src a + dst (255 - a) + 128, out = (t + (t >> 8)) >> 8 on every destination channel.
+ *   rohm_image_overlay     render_img_overlay: src's rgb where src alpha > 0, dst_rgb elsewhere -> out [.., 3].
+ *   rohm_image_flip_lr     Image.FLIP_LEFT_RIGHT on rows x W pixels of `channels` bytes; in and out must differ. */
+int rohm_vertex_normals(const float* verts, const int* faces, const int* offsets, const int* face_ids, int n_mesh, int V,
+                        int F, float* normals, rohm_stream_t stream);
+size_t rohm_color_workspace_bytes(int n_mesh, int F, int W, int H);
+int rohm_color_render(const float* verts, const int* faces, int n_mesh, int V, int F, const float* transform, double fx,
+                      double fy, double cx, double cy, int W, int H, double znear, double zfar, int cull_backfaces,
+                      const float* normals, const unsigned char* colors, int colors_per_mesh, float ambient, float diffuse,
+                      unsigned char* rgba, float* depth, int* face_id, void* ws, size_t ws_bytes, rohm_stream_t stream);
+int rohm_skeleton_mesh(const float* joints, int N, int J, const float* sphere, int Vs, const float* cylinder, int Vc,
+                       const int* limbs, int L, float r_joint, float r_limb, const unsigned char* hide, float* verts,
+                       rohm_stream_t stream);
+int rohm_image_requantize(const unsigned char* rgba, float alpha, long long n_pixels, unsigned char* out,
+                          rohm_stream_t stream);
+int rohm_image_paste(unsigned char* dst, int dst_channels, const unsigned char* src_rgba, long long n_pixels,
+                     rohm_stream_t stream);
+int rohm_image_overlay(const unsigned char* dst_rgb, const unsigned char* src_rgba, long long n_pixels, unsigned char* out,
+                       rohm_stream_t stream);
+int rohm_image_flip_lr(const unsigned char* in, long long rows, int W, int channels, unsigned char* out,
+                       rohm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,17 @@ SIGNATURES = {
     'rohm_project_pixels': (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'rohm_joint_occlusion_mask': (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                             C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'rohm_vertex_normals': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p]),
+    'rohm_color_workspace_bytes': (C.c_size_t, [C.c_int] * 4),
+    'rohm_color_render': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_float_p] + [C.c_double] * 4 +
+                          [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
+                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rohm_skeleton_mesh': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                     C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rohm_image_requantize': (C.c_int, [C.c_void_p, C.c_float, C.c_longlong, C.c_void_p, C.c_void_p]),
+    'rohm_image_paste': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    'rohm_image_overlay': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    'rohm_image_flip_lr': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -1,6 +1,6 @@
 """Evaluation metrics of the drivers on the device: AMASS (eval_amass_full.py:67-147) and
 PROX / EgoBody (eval_prox_egobody.py:172-270), plus a headless evaluator of the drivers' pickles
-(`python -m rohm_amd.evaluation`).
+(`python -m rohm_amd.evaluation`), which with `--render` also writes the scripts' pictures (rohm_amd.render).
 
 `amass_metrics` takes what test_amass_full.py:387-429 produces (recovered joints of the clean clips and of the
 reconstruction, the de-normalised representations) as device tensors and returns the quantities the evaluation
@@ -291,9 +291,75 @@ def evaluate_scene(dataset, saved_data_dir, recordings, heights, device='cuda:0'
     return out
 
 
+def _render_body_model(path, dev):
+    from .body_model import SMPLXLayer
+    from .occlusion import _body_model_file
+    return SMPLXLayer.from_npz(_body_model_file(path)).to(dev)
+
+
+def _load_frames(frames_dir, recording, n, size):
+    """`n` already-undistorted colour frames of a recording as uint8 [n, H, W, 3] (and their base names), or None: PIL is
+    needed to decode them, and PROX's own frames would first have to be undistorted and flipped (cv2), which is not done here."""
+    d = os.path.join(frames_dir, recording)
+    if not os.path.isdir(d):
+        d = frames_dir
+    try:
+        from PIL import Image
+    except ImportError:
+        print(f'[rohm_amd.evaluation] PIL is not installed: rendering {recording} over black', file=sys.stderr)
+        return None, None
+    names = sorted(f for f in os.listdir(d) if f.lower().endswith(('.png', '.jpg', '.jpeg')))[:n]
+    if len(names) < n:
+        print(f'[rohm_amd.evaluation] {d} has {len(names)} frames, {n} needed: rendering over black', file=sys.stderr)
+        return None, None
+    imgs = []
+    for f in names:
+        with Image.open(os.path.join(d, f)) as im:
+            imgs.append(np.asarray(im.convert('RGB').resize(size)) if im.size != tuple(size) else np.asarray(im.convert('RGB')))
+    return np.stack(imgs), [os.path.splitext(f)[0] for f in names]
+
+
+def render_scene_recordings(dataset_root, saved_data_dir, recordings, body_model, out_dir, interval=1, size=(1920, 1080),
+                            frames_dir=None, device='cuda:0'):
+    """eval_prox_egobody.py:373-451 for PROX: <out_dir>/mesh_skel/<frame>.png (predicted body, skeleton and contacts over
+    the background) and <out_dir>/input/<frame>.png (the input body over it), one clip at a time.  Reads
+    cam2world/<scene>.json and calibration/Color.json under `dataset_root`, as the script does."""
+    from . import render as R
+    from .render import _clip_verts
+    with open(os.path.join(dataset_root, 'calibration', 'Color.json')) as f:
+        color_cam = json.load(f)
+    for sub in ('mesh_skel', 'input'):
+        os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
+    W, H = int(size[0]), int(size[1])
+    fxy = (color_cam['f'][0] * W / 1920.0, color_cam['f'][1] * H / 1080.0)
+    cxy = (color_cam['c'][0] * W / 1920.0, color_cam['c'][1] * H / 1080.0)
+    for rec in recordings:
+        with open(os.path.join(dataset_root, 'cam2world', rec.split('_')[0] + '.json')) as f:
+            cam2world = np.array(json.load(f), dtype=np.float64)
+        d = _load(os.path.join(saved_data_dir, rec + '.pkl'))
+        joints = np.asarray(d['rec_ric_data_rec_list_from_smpl'], dtype=np.float32)
+        n_seq, T = joints.shape[:2]
+        contact = np.asarray(d['motion_repr_rec_list'])[:, :, -4:] > 0.5
+        frames, names = _load_frames(frames_dir, rec, n_seq * T, (W, H)) if frames_dir else (None, None)
+        for bs in range(0, n_seq, int(interval)):
+            v_rec = _clip_verts(d, 'motion_repr_rec_list', bs, body_model, device)[None]
+            v_in = _clip_verts(d, 'motion_repr_noisy_list', bs, body_model, device)[None]
+            bg = None if frames is None else torch.from_numpy(frames[bs * T:(bs + 1) * T]).to(device)[None]
+            got = R.render_scene_clips(v_rec, v_in, torch.from_numpy(joints[bs:bs + 1]).to(device), body_model.faces, cam2world, fxy,
+                                       cxy, mask_joint_vis=np.asarray(d['mask_joint_vis_list'])[bs:bs + 1, :T],
+                                       contact_lbl=contact[bs:bs + 1], trans_scene2cano=np.asarray(d['trans_scene2cano_list'])[bs:bs + 1],
+                                       size=(W, H), background=bg)
+            for sub, img in zip(('mesh_skel', 'input'), got):
+                host = img[0].cpu().numpy()
+                for t in range(T):
+                    k = bs * T + t
+                    name = names[k] if names else '{}_frame_{:05d}'.format(rec, k)
+                    R.write_png(os.path.join(out_dir, sub, name + '.png'), host[t])
+
+
 def main(argv=None):
-    """Headless counterpart of eval_amass_full.py / eval_prox_egobody.py's metric part: no visualiser, renderer, cv2,
-    smplx or pandas.  Prints the scripts' final lines; --json also writes the numbers."""
+    """Headless counterpart of eval_amass_full.py / eval_prox_egobody.py: the metrics, and with --render the pictures, with
+    no visualiser, pyrender, cv2, smplx or pandas.  Prints the scripts' final lines; --json also writes the numbers."""
     import argparse
     p = argparse.ArgumentParser(prog='python -m rohm_amd.evaluation', description=main.__doc__)
     p.add_argument('--dataset', required=True, choices=['amass', 'prox', 'egobody'])
@@ -307,6 +373,15 @@ def main(argv=None):
     p.add_argument('--dataset_root', help='egobody with --rohm_root: directory of egobody_rohm_info.csv')
     p.add_argument('--device', default=0, type=int)
     p.add_argument('--json', help='also write the numbers here')
+    truth = lambda x: x.lower() in ['true', '1']
+    p.add_argument('--render', nargs='?', const=True, default=False, type=truth,
+                   help='also write pictures (PNG): amass pred|input|gt/seq_%%03d/frame_%%03d.png, prox mesh_skel|input/<frame>.png')
+    p.add_argument('--render_interval', default=100, type=int, help='render every N clips')
+    p.add_argument('--render_save_path', default='render_imgs/render_amass/mask_lower_noise_3', type=str)
+    p.add_argument('--body_model_path', type=str, default='data/body_models/smplx_model', help='--render: path to the SMPL-X model')
+    p.add_argument('--render_size', nargs=2, type=int, default=[1920, 1080], metavar=('W', 'H'))
+    p.add_argument('--vert_segmentation', help="--render, amass 'lower': smplx_vert_segmentation.json (lower body at alpha 0.1)")
+    p.add_argument('--frames_dir', help='--render, prox: already-undistorted colour frames (<dir>/<recording>/*); needs PIL')
     a = p.parse_args(argv)
     dev = f'cuda:{a.device}'
     if a.dataset == 'amass':
@@ -314,6 +389,10 @@ def main(argv=None):
             p.error('--dataset amass needs --saved_data_path')
         m = evaluate_amass(a.saved_data_path, a.mask_scheme, a.traj_mask_ratio, dev)
         lines, numbers = amass_lines(m), {'dataset': 'amass', 'all': m}
+        if a.render:
+            from .render import render_amass
+            render_amass(_load(a.saved_data_path), _render_body_model(a.body_model_path, dev), a.mask_scheme, a.traj_mask_ratio,
+                         a.render_save_path, a.render_interval, tuple(a.render_size), a.vert_segmentation, device=dev)
     else:
         if not a.saved_data_dir:
             p.error(f'--dataset {a.dataset} needs --saved_data_dir')
@@ -326,6 +405,14 @@ def main(argv=None):
         lines = total.lines()
         numbers = {'dataset': a.dataset, 'all': total.summary(), 'recordings': {r: per[r].summary() for r in recs},
                    'floor_heights': heights}
+        if a.render:
+            if a.dataset != 'prox':
+                p.error("--render covers amass and prox; EgoBody's per-view calibration chain is not read here "
+                        '(rohm_amd.render.render_scene_clips is the entry point)')
+            if not a.dataset_root:
+                p.error('--render with --dataset prox needs --dataset_root (cam2world/, calibration/Color.json)')
+            render_scene_recordings(a.dataset_root, a.saved_data_dir, recs, _render_body_model(a.body_model_path, dev),
+                                    a.render_save_path, a.render_interval, tuple(a.render_size), a.frames_dir, dev)
     for ln in lines:
         print(ln)
     if a.json:
