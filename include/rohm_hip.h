@@ -547,6 +547,41 @@ int rohm_traj_rederive(const rohm_smplx_t* h, const float* repr, long long in_st
                        const float* std_out, int B, int T, float* out, long long out_stride_b,
                        long long out_stride_t, long long out_stride_c, rohm_stream_t stream);
 
+/* Test-time clips of a PROX / EgoBody recording (data_loaders/dataloader_video.py:373-403): for every clip
+ * cano_seq_smplx (up_axis 2 = z; data_loaders/motion_representation.py:47-110) or cano_seq_smplx_egobody (up_axis 1 = y;
+ * :113-184), update_globalRT_for_smplx with delta_T = positions[:,0] - transl, and the full 294-channel get_repr_smplx
+ * (:187-282, feet_vel_thre 5e-5), one workgroup per clip on `stream`, no host synchronisation.
+ * joints_world [N,22,3] float32 and smplx_world [N,79] float64 are what rohm_smplx_frames_to_world produces (+ betas,
+ * body_pose); clip c covers frames starts[c] .. starts[c] + clip_len - 1 (device int32 [C]) or, with starts == NULL,
+ * starts at c * (clip_len - overlap).  A window that leaves [0, N) yields NaN outputs for that clip, never a read
+ * outside the arrays.  2 <= clip_len <= 800; C == 0 returns without a launch.
+ * has_preset_floor != 0 uses preset_floor instead of the clip's lowest joint, except that 0.0 counts as "not given"
+ * (`if preset_floor_height:`).  mean294 / std294 (both or neither) normalise the representation.
+ * Outputs (float32): repr [C, clip_len-1, 294], cano_joints [C, clip_len, 22, 3], cano_orient / cano_transl
+ * [C, clip_len, 3], transf [C, 4, 4] (scene -> canonical).  scratch: rohm_clips_scratch_bytes(C, clip_len) bytes, 0
+ * while the float64 canonical joints of a clip fit into LDS (clip_len <= 255). */
+size_t rohm_clips_scratch_bytes(int C, int clip_len);
+int rohm_clips_build(const float* joints_world, const double* smplx_world, int N, const int* starts, int C,
+                     int clip_len, int overlap, int up_axis, int has_preset_floor, double preset_floor,
+                     const float* mean294, const float* std294, float* repr, float* cano_joints, float* cano_orient,
+                     float* cano_transl, float* transf, void* scratch, size_t scratch_bytes, rohm_stream_t stream);
+
+/* dataloader_video.py:441-458 for M keypoints [M,3] (x, y, confidence; device float32): x -> image_width - 1 - x,
+ * cv2.undistortPoints(src, camera_mtx, dist, P = camera_mtx) (five fixed-point iterations of the inverse of the
+ * k1 k2 p1 p2 k3 model), x flipped back; the confidence passes through.  camera_mtx9 (row-major 3x3) and dist5 are HOST
+ * arrays; float64 arithmetic, float32 store.  out may alias keypoints. */
+int rohm_keypoints_undistort(const float* keypoints, long long M, const double* camera_mtx9, const double* dist5,
+                             double image_width, float* out, rohm_stream_t stream);
+
+/* dataloader_video.py:462-484 with the windows of rohm_clips_build read in place: keypoints [N,22,3] (confidence in
+ * column 2), mask_joint [N, mask_cols >= 22] (device float32) -> mask_joint_vis [C, clip_len, 22] =
+ * (conf > 0.2) * mask_joint and mask_vec_vis [C, clip_len, 294]: ones on the trajectory channels and the betas, the joint
+ * masks x3 on local_positions / local_vel and x6 on smplx_body_pose_6d (joints 1..21), and on the contact channels 1
+ * where both foot joints (7 & 10 left, 8 & 11 right) are visible. */
+int rohm_visibility_masks(const float* keypoints, const float* mask_joint, int mask_cols, int N, const int* starts,
+                          int C, int clip_len, int overlap, float* mask_joint_vis, float* mask_vec_vis,
+                          rohm_stream_t stream);
+
 /* AMASS evaluation metrics (eval_amass_full.py:67-147) as per-clip partial sums.  joints_clean / joints_rec
  * [B,T,22,3]; contact_* point at the 4 contact channels of the de-normalised clean / reconstructed representation
  * of frame (b, t) = contact[(b*T + t)*stride + k].  A (frame, joint) counts as occluded if bit `joint` of

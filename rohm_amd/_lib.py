@@ -178,6 +178,13 @@ SIGNATURES = {
     'rohm_traj_rederive': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong] +
                            [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong,
                                                C.c_void_p]),
+    'rohm_clips_scratch_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    'rohm_clips_build': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_double] +
+                         [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p]),
+    'rohm_keypoints_undistort': (C.c_int, [C.c_void_p, C.c_longlong, c_double_p, c_double_p, C.c_double, C.c_void_p,
+                                           C.c_void_p]),
+    'rohm_visibility_masks': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     'rohm_depth_workspace_bytes': (C.c_size_t, [C.c_int] * 4),
     'rohm_depth_render': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_float_p] + [C.c_double] * 4 +
                           [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -16,6 +16,7 @@
 // The reference's R -> axis-angle -> scipy Rodrigues (float64) round trip for the global orientation is the
 // identity on SO(3); the Gram-Schmidt matrix is used directly.
 #include "common.h"
+#include "rot_priv.h"
 #include "smplx_fk.h"
 
 namespace rohm {
@@ -31,25 +32,6 @@ struct FrameState {      // what frame t+1 contributes to frame t, parked in LDS
     float R[9];          // global orientation, row-major
     float tr[3];         // translation
 };
-
-__device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float sub(float a, float b) { return __fsub_rn(a, b); }
-
-__device__ __forceinline__ void cross_rn(const float* a, const float* b, float* o) {
-    o[0] = sub(mul(a[1], b[2]), mul(a[2], b[1]));
-    o[1] = sub(mul(a[2], b[0]), mul(a[0], b[2]));
-    o[2] = sub(mul(a[0], b[1]), mul(a[1], b[0]));
-}
-
-// qrot (quaternion.py:52-71): v + 2 (w (u x v) + u x (u x v)), u = q.xyz
-__device__ __forceinline__ void qrot_rn(const float* q, const float* v, float* o) {
-    float uv[3], uuv[3];
-    cross_rn(q + 1, v, uv);
-    cross_rn(q + 1, uv, uuv);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) o[c] = add(v[c], mul(2.f, add(mul(q[0], uv[c]), uuv[c])));
-}
 
 __global__ __launch_bounds__(256) void traj_rederive_kernel(
     const float* __restrict__ repr, long long isb, long long ist, long long isc, const float* __restrict__ mean_in,
@@ -101,15 +83,7 @@ __global__ __launch_bounds__(256) void traj_rederive_kernel(
         double fw[3] = {-(double)ac[1], (double)ac[0], 0.0};
         const double fn = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(fw[0], fw[0]), __dmul_rn(fw[1], fw[1])), 0.0));
         const float v0[3] = {(float)(fw[0] / fn), (float)(fw[1] / fn), (float)(fw[2] / fn)};
-        // qbetween(forward, +y) in float32 (quaternion.py:385-394)
-        const float v1[3] = {0.f, 1.f, 0.f};
-        float v[3];
-        cross_rn(v0, v1, v);
-        const float n0 = add(add(mul(v0[0], v0[0]), mul(v0[1], v0[1])), mul(v0[2], v0[2]));
-        const float dt = add(add(mul(v0[0], v1[0]), mul(v0[1], v1[1])), mul(v0[2], v1[2]));
-        const float w = add(sqrtf(mul(n0, 1.f)), dt);
-        const float qn = sqrtf(add(add(add(mul(w, w), mul(v[0], v[0])), mul(v[1], v[1])), mul(v[2], v[2])));
-        s.q[0] = __fdiv_rn(w, qn); s.q[1] = __fdiv_rn(v[0], qn); s.q[2] = __fdiv_rn(v[1], qn); s.q[3] = __fdiv_rn(v[2], qn);
+        qbetween_y_rn(v0, s.q);                                                    // float32 (quaternion.py:385-394)
         if (isnan(s.q[0]) || isnan(s.q[1]) || isnan(s.q[2]) || isnan(s.q[3])) atomicMin(first_nan, t);
         st[t] = s;
     }
@@ -132,11 +106,8 @@ __global__ __launch_bounds__(256) void traj_rederive_kernel(
         const FrameState a = st[t], n = st[t + 1];
         double ch[kTrajCh];
         ch[0] = (double)atan2f(a.q[3], a.q[0]);                                    // root_rot_angle
-        // qmul(q[t+1], qinv(q[t])) (quaternion.py:31-49): terms[i][j] = r_i q_j with r = qinv(q[t]), q = q[t+1]
-        const float r[4] = {a.q[0], -a.q[1], -a.q[2], -a.q[3]};
-        const float* q = n.q;
-        const float vw = sub(sub(sub(mul(r[0], q[0]), mul(r[1], q[1])), mul(r[2], q[2])), mul(r[3], q[3]));
-        const float vz = add(add(sub(mul(r[0], q[3]), mul(r[1], q[2])), mul(r[2], q[1])), mul(r[3], q[0]));
+        float vw, vz;
+        qmul_inv_wz_rn(n.q, a.q, vw, vz);                                          // qmul(q[t+1], qinv(q[t]))
         ch[1] = (double)atan2f(vz, vw);                                            // root_rot_angle_vel
         ch[2] = a.p0[0]; ch[3] = a.p0[1];                                          // root_l_pos
         const float dp[3] = {sub(n.p0[0], a.p0[0]), sub(n.p0[1], a.p0[1]), sub(n.p0[2], a.p0[2])};

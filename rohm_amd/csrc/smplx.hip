@@ -16,6 +16,7 @@
 // the Gram-Schmidt matrices directly (agreement with the full chain is checked against the oracle).
 #include <vector>
 #include "common.h"
+#include "rot_priv.h"
 #include "smplx_fk.h"
 
 namespace rohm {
@@ -386,46 +387,6 @@ __global__ __launch_bounds__(64) void smplx_joints_kernel(const float* __restric
 // global orientation / translation re-expressed in the world frame; float64 numpy + scipy Rotation).  Here: one thread
 // per frame, FK in float32 (as smplx computes it), the rigid-transform part in float64 with scipy's own formulas
 // (from_rotvec / from_matrix / as_rotvec incl. their small-angle series) so results agree to rounding.
-__device__ __forceinline__ void rotvec_to_matrix_f64(const double* rv, double* M) {
-    const double a2 = rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2];
-    const double a = sqrt(a2);
-    const double sc = (a <= 1e-3) ? 0.5 - a2 / 48.0 + a2 * a2 / 3840.0 : sin(a / 2.0) / a;
-    const double x = sc * rv[0], y = sc * rv[1], z = sc * rv[2], w = cos(a / 2.0);
-    const double x2 = x * x, y2 = y * y, z2 = z * z, w2 = w * w;
-    const double xy = x * y, zw = z * w, xz = x * z, yw = y * w, yz = y * z, xw = x * w;
-    M[0] = x2 - y2 - z2 + w2; M[1] = 2 * (xy - zw);       M[2] = 2 * (xz + yw);
-    M[3] = 2 * (xy + zw);       M[4] = -x2 + y2 - z2 + w2; M[5] = 2 * (yz - xw);
-    M[6] = 2 * (xz - yw);       M[7] = 2 * (yz + xw);       M[8] = -x2 - y2 + z2 + w2;
-}
-
-__device__ __forceinline__ void matrix_to_rotvec_f64(const double* M, double* rv) {
-    // scipy Rotation.from_matrix (Markley's quaternion extraction) followed by as_rotvec
-    double dec[4] = {M[0], M[4], M[8], M[0] + M[4] + M[8]};
-    int choice = 0;
-    for (int i = 1; i < 4; ++i)
-        if (dec[i] > dec[choice]) choice = i;
-    double q[4];
-    if (choice != 3) {
-        const int i = choice, j = (i + 1) % 3, k = (j + 1) % 3;
-        q[i] = 1 - dec[3] + 2 * M[i * 3 + i];
-        q[j] = M[j * 3 + i] + M[i * 3 + j];
-        q[k] = M[k * 3 + i] + M[i * 3 + k];
-        q[3] = M[k * 3 + j] - M[j * 3 + k];
-    } else {
-        q[0] = M[7] - M[5];
-        q[1] = M[2] - M[6];
-        q[2] = M[3] - M[1];
-        q[3] = 1 + dec[3];
-    }
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    for (int i = 0; i < 4; ++i) q[i] /= n;
-    if (q[3] < 0) for (int i = 0; i < 4; ++i) q[i] = -q[i];
-    const double ang = 2 * atan2(sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]), q[3]);
-    const double a2 = ang * ang;
-    const double sc = (ang <= 1e-3) ? 2 + a2 / 12 + 7 * a2 * a2 / 2880 : ang / sin(ang / 2);
-    rv[0] = sc * q[0]; rv[1] = sc * q[1]; rv[2] = sc * q[2];
-}
-
 __global__ __launch_bounds__(64) void frames_to_world_kernel(const float* __restrict__ global_orient,
                                                              const float* __restrict__ body_pose,
                                                              const float* __restrict__ betas,

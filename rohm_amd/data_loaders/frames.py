@@ -2,9 +2,10 @@
 
 `data_loaders/dataloader_video.py:116-142` (PROX) and `:274-325` (EgoBody) call the body model ONCE PER FRAME while
 they read a recording (plus a cam2world transform and `update_globalRT_for_smplx` per frame);
-`data_loaders/dataloader_amass.py:194-206` calls it once per clip on the noise-perturbed parameters.  The loaders
-themselves (file formats, pickles, OpenPose json) are out of scope; these two functions take the arrays the loaders
-hold at those lines and return what those lines produce, for all frames in one launch."""
+`data_loaders/dataloader_amass.py:194-206` calls it once per clip on the noise-perturbed parameters.  These two
+functions take the arrays the loaders hold at those lines and return what those lines produce, for all frames in one
+launch.  The test-time loader around the first one is `dataloader_video.DataloaderVideo` (files read on the host, clips
+built by `clips.build_clips` from what `frames_to_world` returns); the AMASS training loader stays the reference's."""
 from __future__ import annotations
 
 import numpy as np

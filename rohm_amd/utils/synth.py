@@ -298,3 +298,89 @@ def synthetic_camera_batch(seed, B, frames=145):
 
 SYNTH_CAM_R = [[0.99, 0.1, 0.05], [-0.1, 0.98, 0.02], [-0.04, -0.03, 1.0]]
 SYNTH_CAM_T = [[0.1, -0.2, 0.3]]
+
+
+def _fk_np(body_tensors, Rg, body_pose, betas, transl):
+    """Joints 0..21 [N,22,3] (float64) of the synthetic body model: rest joints from the shaped template, forward
+    kinematics with the root rotation matrices Rg [N,3,3] and axis-angle body_pose [N,63], plus transl."""
+    N = Rg.shape[0]
+    vt = body_tensors['v_template'].double().numpy()
+    sd = body_tensors['shapedirs'].double().numpy()[:, :, :betas.shape[1]]
+    jreg = body_tensors['J_regressor'].double().numpy()[:22]
+    rest = (jreg @ vt)[None] + np.einsum('jck,nk->njc', np.einsum('jv,vck->jck', jreg, sd), betas)
+    Rl = np.concatenate([Rg[:, None], _rodrigues_np(body_pose.reshape(-1, 3)).reshape(N, 21, 3, 3)], axis=1)
+    Rw, out = [None] * 22, np.zeros((N, 22, 3))
+    for j in range(22):
+        p = SMPLX_PARENTS[j]
+        if j == 0:
+            Rw[0], out[:, 0] = Rl[:, 0], rest[:, 0]
+        else:
+            Rw[j] = Rw[p] @ Rl[:, j]
+            out[:, j] = out[:, p] + np.einsum('nab,nb->na', Rw[p], rest[:, j] - rest[:, p])
+    return out + transl[:, None]
+
+
+def synthetic_recording(seed, N, up_axis='z', degenerate_frames=()):
+    """A recording as `frames_to_world` returns it: (joints_world [N,22,3] float32, smplx_world [N,79] float64 =
+    global_orient, transl, betas, body_pose), z or y up, for the clip builder's tests and fixtures.
+
+    Slow sinusoids (0.1-0.5 Hz at 30 fps): a yaw of +-0.6 rad on top of the rotation that turns the rest body's
+    hip+shoulder axis onto +x, body pose +-0.12 rad, a root drift of +-0.3 m, constant betas; joints from forward
+    kinematics of the synthetic body model.  The four foot joints (7, 10, 8, 11) are then overwritten so that the
+    foot-contact labels of `get_repr_smplx` take both values with decisions far from its thresholds (the synthetic
+    body's feet are not at its bottom): 5-frame phases, staggered per joint, alternate between exactly still and
+    2 cm / frame, and 7-frame phases put the joint 0.03-0.06 m above the recording's lowest point or 0.30 m above it.
+    `degenerate_frames`: frames whose hips and shoulders are moved onto the pelvis's horizontal position, so that they
+    have no facing direction."""
+    g = _rng(seed + 4001)
+    bt = synthetic_smplx_tensors(0)
+    jr = bt['J_regressor'].double().numpy() @ bt['v_template'].double().numpy()
+    a = (jr[1] - jr[2]) + (jr[17] - jr[16])
+    a /= np.linalg.norm(a)
+    ax = np.cross(a, [1.0, 0.0, 0.0])
+    sn, cs = np.linalg.norm(ax), float(a[0])
+    R0 = _rodrigues_np((ax / max(sn, 1e-12) * np.arctan2(sn, cs))[None])[0]
+    t = np.arange(N) / 30.0
+
+    def slow(tail, amp):
+        f = g.uniform(0.1, 0.5, size=tail)
+        ph = g.uniform(0, 2 * np.pi, size=tail)
+        return amp * np.sin(2 * np.pi * f * t.reshape((N,) + (1,) * len(tail)) + ph)
+    yaw = slow((), 0.6)
+    Rz = np.zeros((N, 3, 3))
+    Rz[:, 0, 0], Rz[:, 0, 1], Rz[:, 1, 0], Rz[:, 1, 1], Rz[:, 2, 2] = np.cos(yaw), -np.sin(yaw), np.sin(yaw), np.cos(yaw), 1.0
+    U = np.eye(3) if up_axis == 'z' else np.array([[1.0, 0, 0], [0, 0, 1.0], [0, -1.0, 0]])      # z up -> y up
+    up = 2 if up_axis == 'z' else 1
+    Rg = U @ Rz @ R0
+    body_pose = slow((63,), 0.12).astype(np.float32).astype(np.float64)
+    betas = np.repeat((g.standard_normal((1, 10)) * 0.3).astype(np.float32).astype(np.float64), N, axis=0)
+    drift = slow((3,), 0.3) @ U.T
+    joints = _fk_np(bt, Rg, body_pose, betas, np.zeros((N, 3)))
+    transl = (U @ np.array([0.3, -0.2, 0.0]))[None] + drift
+    joints = joints + transl[:, None]
+    # global orientation as a rotation vector (angles stay well inside (0, pi))
+    ang = np.arccos(np.clip((np.trace(Rg, axis1=1, axis2=2) - 1) / 2, -1, 1))
+    vee = np.stack([Rg[:, 2, 1] - Rg[:, 1, 2], Rg[:, 0, 2] - Rg[:, 2, 0], Rg[:, 1, 0] - Rg[:, 0, 1]], -1)
+    go = vee / (2 * np.sin(ang))[:, None] * ang[:, None]
+    # feet
+    feet = [7, 10, 8, 11]
+    others = [j for j in range(22) if j not in feet]
+    lowest = joints[:, others, up].min()
+    hdir = [k for k in range(3) if k != up]
+    for i, j in enumerate(feet):
+        pos = joints[0, j].copy()
+        direction = g.uniform(0, 2 * np.pi)
+        low = 0.03 + 0.03 * g.uniform(size=N // 7 + 4)
+        for f in range(N):
+            if f > 0 and ((f + 2 * i) // 5) % 2 == 1:
+                sign = 1.0 if ((f + 2 * i) // 10) % 2 == 0 else -1.0          # there and back: the foot stays near the body
+                pos[hdir[0]] += sign * 0.02 * np.cos(direction)
+                pos[hdir[1]] += sign * 0.02 * np.sin(direction)
+            ph = (f + 3 * i) // 7
+            pos[up] = lowest + (low[ph] if ph % 2 == 0 else 0.30)
+            joints[f, j] = pos
+    for f in degenerate_frames:
+        for k in hdir:
+            joints[f, [1, 2, 16, 17], k] = joints[f, 0, k]
+    world = np.concatenate([go, transl, betas, body_pose], axis=-1)
+    return joints.astype(np.float32), world
