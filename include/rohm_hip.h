@@ -566,6 +566,57 @@ int rohm_clips_build(const float* joints_world, const double* smplx_world, int N
                      const float* mean294, const float* std294, float* repr, float* cano_joints, float* cano_orient,
                      float* cano_transl, float* transf, void* scratch, size_t scratch_bytes, rohm_stream_t stream);
 
+/* rohm_clips_build with one more output: orient_transl64 [C, clip_len, 6] (float64; may be NULL), the canonical
+ * global_orient and transl before their float32 store -- data_loaders/dataloader_amass.py keeps them in float64 up to the
+ * body-model call (:152-197).  Same kernel; every other output is bit-identical to rohm_clips_build's. */
+int rohm_clips_build_f64(const float* joints_world, const double* smplx_world, int N, const int* starts, int C,
+                         int clip_len, int overlap, int up_axis, int has_preset_floor, double preset_floor,
+                         const float* mean294, const float* std294, float* repr, float* cano_joints, float* cano_orient,
+                         float* cano_transl, float* transf, double* orient_transl64, void* scratch, size_t scratch_bytes,
+                         rohm_stream_t stream);
+
+/* get_repr_smplx (data_loaders/motion_representation.py:187-282, feet_vel_thre 5e-5) on clips that are canonical already
+ * -- the second half of rohm_clips_build: positions [C, clip_len, 22, 3] (float32, or float64 with positions_f64 != 0),
+ * params [C, clip_len, 79] float64 (global_orient, transl, betas, body_pose) -> repr [C, clip_len-1, 294] float32.  What
+ * the reference computes in the joints' dtype (across vector, position differences, squared foot velocities) is float32
+ * arithmetic for float32 positions and float64 arithmetic for float64 ones; NaN handling, mean294 / std294, the LDS /
+ * scratch rule (rohm_clips_scratch_bytes) and the limits on clip_len are those of rohm_clips_build.
+ * joint_noise [C, clip_len, 22, 3] (float64; may be NULL): the joints become float32(positions + joint_noise) first
+ * (dataloader_amass.py:305-307).  joints_out (float32; may be NULL) receives the joints the representation was made of. */
+int rohm_clips_repr(const void* positions, int positions_f64, const double* params, const double* joint_noise, int C,
+                    int clip_len, const float* mean294, const float* std294, float* repr, float* joints_out, void* scratch,
+                    size_t scratch_bytes, rohm_stream_t stream);
+
+/* SMPL-X parameter noise of the AMASS loader (dataloader_amass.py:156-192), float64 throughout, one thread per rotation:
+ * params / out [M,79] rows (global_orient, transl, betas, body_pose); noise_orient [M,3] and noise_pose [M,63] are in
+ * degrees and are added to the 'zxy' Euler angles scipy's lowercase (extrinsic) as_euler gives, the result going back
+ * through from_euler(...).as_rotvec() (rotation angle in [0, pi]); noise_transl [M,3] and noise_betas [M,10] are added.
+ * additive != 0 adds all four arrays to the parameters as they are (the sep_noise items, :298-303).  The kernel draws
+ * nothing; out must not alias params. */
+int rohm_smplx_param_noise(const double* params, const double* noise_orient, const double* noise_transl,
+                           const double* noise_betas, const double* noise_pose, long long M, int additive, double* out,
+                           rohm_stream_t stream);
+
+/* Per-channel mean and population standard deviation of repr [rows, 294] (float32; dataloader_amass.py:254-258) into
+ * mean294 / std294 (device float64 [294]).  float64 accumulation in two stages -- per-workgroup (mean, sum of squared
+ * deviations) of a block of rows, then one workgroup that folds them in order -- so the result is bitwise reproducible.
+ * scratch: rohm_repr_stats_scratch_bytes(rows) bytes. */
+size_t rohm_repr_stats_scratch_bytes(long long rows);
+int rohm_repr_stats(const float* repr, long long rows, double* mean294, double* std294, void* scratch, size_t scratch_bytes,
+                    rohm_stream_t stream);
+
+/* dataloader_amass.py:317-339 for the B items index[b] (device int64; an index outside [0, n_items) gives NaN rows):
+ * repr_clean / repr_noisy [n_items, rows_per_item, 294] de-normalised (repr_noisy NULL: input_noise = False, the noisy
+ * item is the clean one; with noisy_per_batch != 0 it is [B, rows_per_item, 294], row b for batch entry b: the sep_noise
+ * items, which are made per batch) -> out_clean, out_noisy [B, rows_per_item, 294] = (x - mean) / std in float64, rounded once.
+ * The first overwrite_channels noisy channels are taken from the clean item before normalising (task 'pose', :324).
+ * cond_kind 1: cond [B, rows, 22] = the first 22 noisy channels; 2: cond [B, rows, 13] = channels 0, 2, 3, 6, 7..12,
+ * 16..18 (:337); 0: none.  control_cond [B, rows, 272] (may be NULL) = the last 272 clean channels. */
+int rohm_amass_batch(const float* repr_clean, const float* repr_noisy, long long n_items, int rows_per_item,
+                     const long long* index, int B, const float* mean294, const float* std294, int overwrite_channels,
+                     int noisy_per_batch, int cond_kind, float* out_clean, float* out_noisy, float* cond, float* control_cond,
+                     rohm_stream_t stream);
+
 /* dataloader_video.py:441-458 for M keypoints [M,3] (x, y, confidence; device float32): x -> image_width - 1 - x,
  * cv2.undistortPoints(src, camera_mtx, dist, P = camera_mtx) (five fixed-point iterations of the inverse of the
  * k1 k2 p1 p2 k3 model), x flipped back; the confidence passes through.  camera_mtx9 (row-major 3x3) and dist5 are HOST

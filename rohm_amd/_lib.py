@@ -181,6 +181,15 @@ SIGNATURES = {
     'rohm_clips_scratch_bytes': (C.c_size_t, [C.c_int, C.c_int]),
     'rohm_clips_build': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_double] +
                          [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p]),
+    'rohm_clips_build_f64': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_double] +
+                             [C.c_void_p] * 9 + [C.c_size_t, C.c_void_p]),
+    'rohm_clips_repr': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 +
+                        [C.c_size_t, C.c_void_p]),
+    'rohm_smplx_param_noise': (C.c_int, [C.c_void_p] * 5 + [C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
+    'rohm_repr_stats_scratch_bytes': (C.c_size_t, [C.c_longlong]),
+    'rohm_repr_stats': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rohm_amass_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
     'rohm_keypoints_undistort': (C.c_int, [C.c_void_p, C.c_longlong, c_double_p, c_double_p, C.c_double, C.c_void_p,
                                            C.c_void_p]),
     'rohm_visibility_masks': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,

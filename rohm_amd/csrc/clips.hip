@@ -46,6 +46,7 @@ struct ClipArgs {
     float* cano_orient;       // [C,L,3]
     float* cano_transl;       // [C,L,3]
     float* transf;            // [C,4,4]
+    double* orient_transl64;  // [C,L,6] canonical global_orient, transl before the float32 store, or null
     double* scratch;          // [C,L,66] when the joints do not fit into LDS, else null
 };
 
@@ -56,6 +57,125 @@ __device__ __forceinline__ void mat3_vec(const double* M, const double* v, doubl
 
 __device__ __forceinline__ double dsq3(double a, double b, double c) {      // x**2 + y**2 + z**2, left to right, no fma
     return __dadd_rn(__dadd_rn(__dmul_rn(a, a), __dmul_rn(b, b)), __dmul_rn(c, c));
+}
+
+// get_repr_smplx (:187-282) on canonical joints cj [L,22,3] (float64 storage, LDS or scratch), the rotation matrices sR [L,9]
+// and translations sT [L,3] of the canonical global_orient / transl, and parameter rows W [L,79] (betas, body_pose); sQ [L,4]
+// and first_nan (== L on entry) are workgroup storage.  All of it must be visible to the workgroup on entry.  F32: the joints
+// are float32 values (the noisy joints of the AMASS loader), so what the reference computes in the joints' dtype -- the
+// across vector and its normalisation, the differences behind local_positions / local_vel / root_l_vel and the squared
+// foot velocities -- is float32 arithmetic without fma contraction.
+template <bool F32>
+__device__ __forceinline__ void repr_from_canonical(const double* cj, const double* sR, const double* sT, float* sQ, int* first_nan,
+                                                    const double* W, int L, const float* mean, const float* stdv, float* o_repr) {
+    const int tid = threadIdx.x;
+    auto dif = [](double x, double y) -> double { return F32 ? (double)sub((float)x, (float)y) : x - y; };
+    auto sq3 = [](double x, double y, double z) -> double {     // x**2 + y**2 + z**2 in the joints' dtype
+        if (!F32) return dsq3(x, y, z);
+        const float fx = (float)x, fy = (float)y, fz = (float)z;
+        return (double)add(add(mul(fx, fx), mul(fy, fy)), mul(fz, fz));
+    };
+    // ---- root quaternion of every frame from the facing direction --------------------------------------------------------
+    for (int f = tid; f < L; f += blockDim.x) {
+        const double* p = cj + (size_t)f * NJ * 3;
+        double ac[3];                                        // (r_hip - l_hip) + (sdr_r - sdr_l) with r_hip = 1, l_hip = 2
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (F32) ac[k] = (double)add(sub((float)p[1 * 3 + k], (float)p[2 * 3 + k]), sub((float)p[17 * 3 + k], (float)p[16 * 3 + k]));
+            else ac[k] = (p[1 * 3 + k] - p[2 * 3 + k]) + (p[17 * 3 + k] - p[16 * 3 + k]);
+        }
+        if (F32) {
+            const float an = __fsqrt_rn((float)sq3(ac[0], ac[1], ac[2]));
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ac[k] = (double)__fdiv_rn((float)ac[k], an);
+        } else {
+            const double an = sqrt(dsq3(ac[0], ac[1], ac[2]));
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ac[k] /= an;
+        }
+        const double fw[3] = {-ac[1], ac[0], 0.0};          // (0,0,1) x across
+        const double fn = sqrt(dsq3(fw[0], fw[1], fw[2]));
+        const float v0[3] = {(float)(fw[0] / fn), (float)(fw[1] / fn), (float)(fw[2] / fn)};
+        float q[4];
+        qbetween_y_rn(v0, q);
+        if (isnan(q[0]) || isnan(q[1]) || isnan(q[2]) || isnan(q[3])) atomicMin(first_nan, f);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sQ[f * 4 + k] = q[k];
+    }
+    __syncthreads();
+    if (tid == 0) {                                          // only the FIRST NaN frame is patched; then frame 0 = identity
+        const int k = *first_nan;
+        if (k < L) {
+            const int src = (k == 0) ? L - 1 : k - 1;
+            for (int i = 0; i < 4; ++i) sQ[k * 4 + i] = sQ[src * 4 + i];
+        }
+        sQ[0] = 1.f; sQ[1] = 0.f; sQ[2] = 0.f; sQ[3] = 0.f;
+    }
+    __syncthreads();
+
+    // ---- phase 2: the 294 channels of frames 0 .. L-2, one (frame, joint) pair per thread ---------------------------------
+    auto put = [&](float* row, int ch, double v) {
+        row[ch] = (float)(mean ? (v - (double)mean[ch]) / (double)stdv[ch] : v);
+    };
+    for (int i = tid; i < (L - 1) * NJ; i += blockDim.x) {
+        const int t = i / NJ, j = i - t * NJ;
+        float* row = o_repr + (size_t)t * C_TOTAL;
+        const double* p = cj + (size_t)t * NJ * 3;
+        const double* pn = p + NJ * 3;
+        const float* q = sQ + t * 4;
+        const float* qn = q + 4;
+        const float lp[3] = {(float)dif(p[j * 3], p[0]), (float)dif(p[j * 3 + 1], p[1]), (float)p[j * 3 + 2]};
+        const float dv[3] = {(float)dif(pn[j * 3], p[j * 3]), (float)dif(pn[j * 3 + 1], p[j * 3 + 1]), (float)dif(pn[j * 3 + 2], p[j * 3 + 2])};
+        float r[3];
+        qrot_rn(q, lp, r);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) put(row, CH_LOCAL + j * 3 + k, r[k]);
+        qrot_rn(q, dv, r);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) put(row, CH_LOCAL_VEL + j * 3 + k, r[k]);
+        const double* w = W + (size_t)t * kWorldCols;
+        if (j > 0) {
+            double M[9];
+            rotvec_to_matrix_f64(w + 16 + (j - 1) * 3, M);
+            const int o = CH_POSE6D + (j - 1) * 6;
+            put(row, o, M[0]); put(row, o + 1, M[1]); put(row, o + 2, M[3]); put(row, o + 3, M[4]); put(row, o + 4, M[6]);
+            put(row, o + 5, M[7]);
+            continue;
+        }
+        put(row, 0, (double)atan2f(q[3], q[0]));                                   // root_rot_angle
+        float vw, vz;
+        qmul_inv_wz_rn(qn, q, vw, vz);
+        put(row, 1, (double)atan2f(vz, vw));                                       // root_rot_angle_vel
+        put(row, 2, p[0]); put(row, 3, p[1]);                                      // root_l_pos
+        qrot_rn(qn, dv, r);                                                        // rotated by the NEXT frame's q
+        put(row, 4, r[0]); put(row, 5, r[1]);                                      // root_l_vel
+        put(row, 6, p[2]);                                                         // root_height
+        const double* R = sR + (size_t)t * 9;
+        const double* Rn = R + 9;
+        put(row, 7, R[0]); put(row, 8, R[1]); put(row, 9, R[3]); put(row, 10, R[4]); put(row, 11, R[6]); put(row, 12, R[7]);
+        double dR[9], Wm[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) dR[k] = Rn[k] - R[k];
+#pragma unroll
+        for (int x = 0; x < 3; ++x)
+#pragma unroll
+            for (int y = 0; y < 3; ++y) Wm[x * 3 + y] = dR[x * 3] * R[y * 3] + dR[x * 3 + 1] * R[y * 3 + 1] + dR[x * 3 + 2] * R[y * 3 + 2];
+        put(row, 13, (-Wm[5] + Wm[7]) / 2.0); put(row, 14, (Wm[2] - Wm[6]) / 2.0); put(row, 15, (-Wm[1] + Wm[3]) / 2.0);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { put(row, 16 + k, sT[t * 3 + k]); put(row, 19 + k, sT[(t + 1) * 3 + k] - sT[t * 3 + k]); }
+#pragma unroll
+        for (int k = 0; k < NBETA; ++k) put(row, CH_BETAS + k, w[6 + k]);
+        // foot contact (foot_detect, :23-44, up_axis 'z'): slow AND low, columns left 7, 10 then right 8, 11
+        const int fj[4] = {7, 10, 8, 11};
+        const double hthr[4] = {0.18, 0.15, 0.18, 0.15};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double* u = p + fj[k] * 3;
+            const double* un = pn + fj[k] * 3;
+            const double sq = sq3(dif(un[0], u[0]), dif(un[1], u[1]), dif(un[2], u[2]));
+            put(row, CH_CONTACT + k, (sq < 5e-5 && u[2] < hthr[k]) ? 1.0 : 0.0);
+        }
+    }
 }
 
 __global__ __launch_bounds__(kClipThreads) void clips_build_kernel(const ClipArgs a) {
@@ -81,6 +201,8 @@ __global__ __launch_bounds__(kClipThreads) void clips_build_kernel(const ClipArg
         for (int i = tid; i < L * NJ * 3; i += blockDim.x) o_cj[i] = nanv;
         for (int i = tid; i < L * 3; i += blockDim.x) { o_go[i] = nanv; o_tr[i] = nanv; }
         if (tid < 16) o_tm[tid] = nanv;
+        if (a.orient_transl64)
+            for (int i = tid; i < L * 6; i += blockDim.x) a.orient_transl64[(size_t)c * L * 6 + i] = __builtin_nan("");
         return;
     }
     const float* J = a.joints + (size_t)s0 * NJ * 3;
@@ -186,102 +308,61 @@ __global__ __launch_bounds__(kClipThreads) void clips_build_kernel(const ClipArg
             sT[f * 3 + k] = t;
             o_go[f * 3 + k] = (float)rvn[k];
             o_tr[f * 3 + k] = (float)t;
+            if (a.orient_transl64) {
+                double* o64 = a.orient_transl64 + ((size_t)c * L + f) * 6;
+                o64[k] = rvn[k];
+                o64[3 + k] = t;
+            }
         }
     }
     __syncthreads();
 
-    // ---- root quaternion of every frame from the facing direction --------------------------------------------------------
+    repr_from_canonical<false>(cj, sR, sT, sQ, first_nan, W, L, a.mean, a.stdv, o_repr);
+}
+
+// get_repr_smplx on joints that are canonical already (the noisy clips of dataloader_amass.py:213-215 and the sep_noise
+// items of :298-309): positions [C,L,22,3] float32 or float64, params [C,L,79] float64 (global_orient, transl, betas,
+// body_pose).  With joint_noise [C,L,22,3] (float64) the joints become float32(positions + noise) first (:305-307).
+struct ReprArgs {
+    const float* pos32;
+    const double* pos64;
+    const double* params;
+    const double* joint_noise;
+    int L;
+    const float* mean;
+    const float* stdv;
+    float* repr;              // [C,L-1,294]
+    float* joints_out;        // [C,L,22,3] the joints the representation was computed from, or null
+    double* scratch;
+};
+
+template <bool F32>
+__global__ __launch_bounds__(kClipThreads) void clips_repr_kernel(const ReprArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const int L = a.L, c = blockIdx.x, tid = threadIdx.x;
+    double* cj = a.scratch ? a.scratch + (size_t)c * L * NJ * 3 : reinterpret_cast<double*>(smem_raw);
+    unsigned char* aux = smem_raw + (a.scratch ? 0 : (size_t)L * kFrameLds);
+    double* sR = reinterpret_cast<double*>(aux);
+    double* sT = sR + (size_t)L * 9;
+    float* sQ = reinterpret_cast<float*>(sT + (size_t)L * 3);
+    int* first_nan = reinterpret_cast<int*>(sQ + (size_t)L * 4 + 8);
+    const size_t base = (size_t)c * L * NJ * 3;
+    const double* W = a.params + (size_t)c * L * kWorldCols;
+    if (tid == 0) *first_nan = L;
+    for (int i = tid; i < L * NJ * 3; i += blockDim.x) {
+        double v = a.pos64 ? a.pos64[base + i] : (double)a.pos32[base + i];
+        if (a.joint_noise) v = (double)(float)(v + a.joint_noise[base + i]);
+        cj[i] = v;
+        if (a.joints_out) a.joints_out[base + i] = (float)v;
+    }
     for (int f = tid; f < L; f += blockDim.x) {
-        const double* p = cj + (size_t)f * NJ * 3;
-        double ac[3];                                        // (r_hip - l_hip) + (sdr_r - sdr_l) with r_hip = 1, l_hip = 2
+        const double* w = W + (size_t)f * kWorldCols;
+        rotvec_to_matrix_f64(w, sR + (size_t)f * 9);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) ac[k] = (p[1 * 3 + k] - p[2 * 3 + k]) + (p[17 * 3 + k] - p[16 * 3 + k]);
-        const double an = sqrt(dsq3(ac[0], ac[1], ac[2]));
-#pragma unroll
-        for (int k = 0; k < 3; ++k) ac[k] /= an;
-        const double fw[3] = {-ac[1], ac[0], 0.0};          // (0,0,1) x across
-        const double fn = sqrt(dsq3(fw[0], fw[1], fw[2]));
-        const float v0[3] = {(float)(fw[0] / fn), (float)(fw[1] / fn), (float)(fw[2] / fn)};
-        float q[4];
-        qbetween_y_rn(v0, q);
-        if (isnan(q[0]) || isnan(q[1]) || isnan(q[2]) || isnan(q[3])) atomicMin(first_nan, f);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) sQ[f * 4 + k] = q[k];
+        for (int k = 0; k < 3; ++k) sT[f * 3 + k] = w[3 + k];
     }
     __syncthreads();
-    if (tid == 0) {                                          // only the FIRST NaN frame is patched; then frame 0 = identity
-        const int k = *first_nan;
-        if (k < L) {
-            const int src = (k == 0) ? L - 1 : k - 1;
-            for (int i = 0; i < 4; ++i) sQ[k * 4 + i] = sQ[src * 4 + i];
-        }
-        sQ[0] = 1.f; sQ[1] = 0.f; sQ[2] = 0.f; sQ[3] = 0.f;
-    }
-    __syncthreads();
-
-    // ---- phase 2: the 294 channels of frames 0 .. L-2, one (frame, joint) pair per thread ---------------------------------
-    auto put = [&](float* row, int ch, double v) {
-        row[ch] = (float)(a.mean ? (v - (double)a.mean[ch]) / (double)a.stdv[ch] : v);
-    };
-    for (int i = tid; i < (L - 1) * NJ; i += blockDim.x) {
-        const int t = i / NJ, j = i - t * NJ;
-        float* row = o_repr + (size_t)t * C_TOTAL;
-        const double* p = cj + (size_t)t * NJ * 3;
-        const double* pn = p + NJ * 3;
-        const float* q = sQ + t * 4;
-        const float* qn = q + 4;
-        const float lp[3] = {(float)(p[j * 3] - p[0]), (float)(p[j * 3 + 1] - p[1]), (float)p[j * 3 + 2]};
-        const float dv[3] = {(float)(pn[j * 3] - p[j * 3]), (float)(pn[j * 3 + 1] - p[j * 3 + 1]), (float)(pn[j * 3 + 2] - p[j * 3 + 2])};
-        float r[3];
-        qrot_rn(q, lp, r);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) put(row, CH_LOCAL + j * 3 + k, r[k]);
-        qrot_rn(q, dv, r);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) put(row, CH_LOCAL_VEL + j * 3 + k, r[k]);
-        const double* w = W + (size_t)t * kWorldCols;
-        if (j > 0) {
-            double M[9];
-            rotvec_to_matrix_f64(w + 16 + (j - 1) * 3, M);
-            const int o = CH_POSE6D + (j - 1) * 6;
-            put(row, o, M[0]); put(row, o + 1, M[1]); put(row, o + 2, M[3]); put(row, o + 3, M[4]); put(row, o + 4, M[6]);
-            put(row, o + 5, M[7]);
-            continue;
-        }
-        put(row, 0, (double)atan2f(q[3], q[0]));                                   // root_rot_angle
-        float vw, vz;
-        qmul_inv_wz_rn(qn, q, vw, vz);
-        put(row, 1, (double)atan2f(vz, vw));                                       // root_rot_angle_vel
-        put(row, 2, p[0]); put(row, 3, p[1]);                                      // root_l_pos
-        qrot_rn(qn, dv, r);                                                        // rotated by the NEXT frame's q
-        put(row, 4, r[0]); put(row, 5, r[1]);                                      // root_l_vel
-        put(row, 6, p[2]);                                                         // root_height
-        const double* R = sR + (size_t)t * 9;
-        const double* Rn = R + 9;
-        put(row, 7, R[0]); put(row, 8, R[1]); put(row, 9, R[3]); put(row, 10, R[4]); put(row, 11, R[6]); put(row, 12, R[7]);
-        double dR[9], Wm[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) dR[k] = Rn[k] - R[k];
-#pragma unroll
-        for (int x = 0; x < 3; ++x)
-#pragma unroll
-            for (int y = 0; y < 3; ++y) Wm[x * 3 + y] = dR[x * 3] * R[y * 3] + dR[x * 3 + 1] * R[y * 3 + 1] + dR[x * 3 + 2] * R[y * 3 + 2];
-        put(row, 13, (-Wm[5] + Wm[7]) / 2.0); put(row, 14, (Wm[2] - Wm[6]) / 2.0); put(row, 15, (-Wm[1] + Wm[3]) / 2.0);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { put(row, 16 + k, sT[t * 3 + k]); put(row, 19 + k, sT[(t + 1) * 3 + k] - sT[t * 3 + k]); }
-#pragma unroll
-        for (int k = 0; k < NBETA; ++k) put(row, CH_BETAS + k, w[6 + k]);
-        // foot contact (foot_detect, :23-44, up_axis 'z'): slow AND low, columns left 7, 10 then right 8, 11
-        const int fj[4] = {7, 10, 8, 11};
-        const double hthr[4] = {0.18, 0.15, 0.18, 0.15};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const double* u = p + fj[k] * 3;
-            const double* un = pn + fj[k] * 3;
-            const double sq = dsq3(un[0] - u[0], un[1] - u[1], un[2] - u[2]);
-            put(row, CH_CONTACT + k, (sq < 5e-5 && u[2] < hthr[k]) ? 1.0 : 0.0);
-        }
-    }
+    repr_from_canonical<F32>(cj, sR, sT, sQ, first_nan, W, L, a.mean, a.stdv, a.repr + (size_t)c * (L - 1) * C_TOTAL);
 }
 
 // dataloader_video.py:441-458: flip x, cv2.undistortPoints(src, K, dist, P = K) (five fixed-point iterations of the inverse of
@@ -356,11 +437,11 @@ extern "C" size_t rohm_clips_scratch_bytes(int C, int L) {
     return clip_lds_bytes(L, true) <= (size_t)kLdsMax ? 0 : (size_t)C * L * NJ * 3 * sizeof(double);
 }
 
-extern "C" int rohm_clips_build(const float* joints_world, const double* smplx_world, int N, const int* starts, int C,
-                                int clip_len, int overlap, int up_axis, int has_preset_floor, double preset_floor,
-                                const float* mean294, const float* std294, float* repr, float* cano_joints,
-                                float* cano_orient, float* cano_transl, float* transf, void* scratch, size_t scratch_bytes,
-                                rohm_stream_t stream) {
+extern "C" int rohm_clips_build_f64(const float* joints_world, const double* smplx_world, int N, const int* starts, int C,
+                                    int clip_len, int overlap, int up_axis, int has_preset_floor, double preset_floor,
+                                    const float* mean294, const float* std294, float* repr, float* cano_joints,
+                                    float* cano_orient, float* cano_transl, float* transf, double* orient_transl64,
+                                    void* scratch, size_t scratch_bytes, rohm_stream_t stream) {
     ROHM_ARG_CHECK(clip_len >= 2 && clip_len <= 800, "clips_build: need 2 <= clip_len <= 800 (got %d)", clip_len);
     ROHM_ARG_CHECK(C >= 0 && N >= 0, "clips_build: negative size (C=%d N=%d)", C, N);
     ROHM_ARG_CHECK(up_axis == 1 || up_axis == 2, "clips_build: up_axis must be 1 (y) or 2 (z)");
@@ -385,7 +466,8 @@ extern "C" int rohm_clips_build(const float* joints_world, const double* smplx_w
             for (int j = 0; j < 3; ++j) a.A[i * 3 + j] = rz[i * 3] * rx[j] + rz[i * 3 + 1] * rx[3 + j] + rz[i * 3 + 2] * rx[6 + j];
     }
     a.mean = mean294; a.stdv = std294; a.repr = repr; a.cano_joints = cano_joints; a.cano_orient = cano_orient;
-    a.cano_transl = cano_transl; a.transf = transf; a.scratch = need ? static_cast<double*>(scratch) : nullptr;
+    a.cano_transl = cano_transl; a.transf = transf; a.orient_transl64 = orient_transl64;
+    a.scratch = need ? static_cast<double*>(scratch) : nullptr;
     const size_t lds = clip_lds_bytes(clip_len, need == 0);
     static int lds_set = 0;
     if ((int)lds > lds_set) {
@@ -395,6 +477,47 @@ extern "C" int rohm_clips_build(const float* joints_world, const double* smplx_w
     }
     prof::Scope ps("clips_build", 0.0, (double)C * clip_len * (4.0 * 66 * 2 + 8.0 * kWorldCols + 4.0 * C_TOTAL), (hipStream_t)stream);
     hipLaunchKernelGGL(clips_build_kernel, dim3(C), dim3(kClipThreads), lds, (hipStream_t)stream, a);
+    ROHM_LAUNCH_CHECK();
+    return ROHM_OK;
+}
+
+extern "C" int rohm_clips_build(const float* joints_world, const double* smplx_world, int N, const int* starts, int C,
+                                int clip_len, int overlap, int up_axis, int has_preset_floor, double preset_floor,
+                                const float* mean294, const float* std294, float* repr, float* cano_joints,
+                                float* cano_orient, float* cano_transl, float* transf, void* scratch, size_t scratch_bytes,
+                                rohm_stream_t stream) {
+    return rohm_clips_build_f64(joints_world, smplx_world, N, starts, C, clip_len, overlap, up_axis, has_preset_floor,
+                                preset_floor, mean294, std294, repr, cano_joints, cano_orient, cano_transl, transf, nullptr,
+                                scratch, scratch_bytes, stream);
+}
+
+extern "C" int rohm_clips_repr(const void* positions, int positions_f64, const double* params, const double* joint_noise, int C,
+                               int clip_len, const float* mean294, const float* std294, float* repr, float* joints_out,
+                               void* scratch, size_t scratch_bytes, rohm_stream_t stream) {
+    ROHM_ARG_CHECK(clip_len >= 2 && clip_len <= 800, "clips_repr: need 2 <= clip_len <= 800 (got %d)", clip_len);
+    ROHM_ARG_CHECK(C >= 0, "clips_repr: negative size (C=%d)", C);
+    ROHM_ARG_CHECK((mean294 == nullptr) == (std294 == nullptr), "clips_repr: pass both mean and std or neither");
+    if (C == 0) return ROHM_OK;
+    ROHM_ARG_CHECK(positions && params && repr, "clips_repr: null argument");
+    const size_t need = rohm_clips_scratch_bytes(C, clip_len);
+    ROHM_ARG_CHECK(need == 0 || (scratch && scratch_bytes >= need), "clips_repr: scratch too small (%zu < %zu)", scratch_bytes, need);
+    ReprArgs a;
+    a.pos32 = positions_f64 ? nullptr : static_cast<const float*>(positions);
+    a.pos64 = positions_f64 ? static_cast<const double*>(positions) : nullptr;
+    a.params = params; a.joint_noise = joint_noise; a.L = clip_len; a.mean = mean294; a.stdv = std294; a.repr = repr;
+    a.joints_out = joints_out; a.scratch = need ? static_cast<double*>(scratch) : nullptr;
+    const bool f32 = !positions_f64 || joint_noise;            // the dtype get_repr_smplx sees
+    const size_t lds = clip_lds_bytes(clip_len, need == 0);
+    static int lds_set[2] = {0, 0};
+    if ((int)lds > lds_set[f32]) {
+        const void* fn = f32 ? reinterpret_cast<const void*>(&clips_repr_kernel<true>)
+                             : reinterpret_cast<const void*>(&clips_repr_kernel<false>);
+        ROHM_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        lds_set[f32] = (int)lds;
+    }
+    prof::Scope ps("clips_repr", 0.0, (double)C * clip_len * (8.0 * 66 + 8.0 * kWorldCols + 4.0 * C_TOTAL), (hipStream_t)stream);
+    if (f32) hipLaunchKernelGGL(clips_repr_kernel<true>, dim3(C), dim3(kClipThreads), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(clips_repr_kernel<false>, dim3(C), dim3(kClipThreads), lds, (hipStream_t)stream, a);
     ROHM_LAUNCH_CHECK();
     return ROHM_OK;
 }

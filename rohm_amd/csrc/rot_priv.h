@@ -47,6 +47,34 @@ __device__ __forceinline__ void matrix_to_rotvec_f64(const double* M, double* rv
     rv[0] = sc * q[0]; rv[1] = sc * q[1]; rv[2] = sc * q[2];
 }
 
+// scipy Rotation.from_rotvec(rv).as_euler('zxy', degrees=True): extrinsic rotations about z, x, y, i.e.
+// R = Ry(e[2]) Rx(e[1]) Rz(e[0]); first and third angle in [-180, 180], the middle one in [-90, 90]
+__device__ __forceinline__ void rotvec_to_euler_zxy_deg_f64(const double* rv, double* e) {
+    double M[9];
+    rotvec_to_matrix_f64(rv, M);
+    const double k = 180.0 / M_PI;
+    e[0] = atan2(M[3], M[4]) * k;
+    e[1] = asin(fmin(1.0, fmax(-1.0, -M[5]))) * k;
+    e[2] = atan2(M[2], M[8]) * k;
+}
+
+// scipy Rotation.from_euler('zxy', e, degrees=True).as_rotvec(): q = qy qx qz, w >= 0, rotation angle in [0, pi]
+__device__ __forceinline__ void euler_zxy_deg_to_rotvec_f64(const double* e, double* rv) {
+    const double k = M_PI / 360.0;
+    const double ca = cos(e[0] * k), sa = sin(e[0] * k), cb = cos(e[1] * k), sb = sin(e[1] * k);
+    const double cc = cos(e[2] * k), sc = sin(e[2] * k);
+    // qx qz = (cb ca, sb ca, -sb sa, cb sa); then qy = (cc, 0, sc, 0) from the left
+    const double w1 = cb * ca, x1 = sb * ca, y1 = -sb * sa, z1 = cb * sa;
+    double q[4] = {cc * x1 + sc * z1, cc * y1 + sc * w1, cc * z1 - sc * x1, cc * w1 - sc * y1};   // x, y, z, w
+    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int i = 0; i < 4; ++i) q[i] /= n;
+    if (q[3] < 0) for (int i = 0; i < 4; ++i) q[i] = -q[i];
+    const double ang = 2 * atan2(sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]), q[3]);
+    const double a2 = ang * ang;
+    const double sc2 = (ang <= 1e-3) ? 2 + a2 / 12 + 7 * a2 * a2 / 2880 : ang / sin(ang / 2);
+    rv[0] = sc2 * q[0]; rv[1] = sc2 * q[1]; rv[2] = sc2 * q[2];
+}
+
 __device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
 __device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
 __device__ __forceinline__ float sub(float a, float b) { return __fsub_rn(a, b); }

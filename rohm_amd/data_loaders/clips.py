@@ -52,8 +52,18 @@ def _windows(starts, n_frames, clip_len, overlap_len, device):
     return st, int(st.shape[0])
 
 
+def _stats_tensors(stats, device):
+    if stats is None:
+        return None, None
+    mean, std = (torch.as_tensor(np.asarray(s, dtype=np.float32) if not torch.is_tensor(s) else s).to(
+        device=device, dtype=torch.float32).contiguous() for s in stats)
+    if mean.shape != (294,) or std.shape != (294,):
+        raise ValueError('stats must be (Mean [294], Std [294])')
+    return mean, std
+
+
 def build_clips(joints_world, smplx_world, clip_len, overlap_len=2, up_axis='z', preset_floor_height=None, stats=None,
-                starts=None):
+                starts=None, params_f64=False):
     """All clips of a recording: canonicalise, re-express the SMPL-X parameters, compute the motion representation.
 
     joints_world [N,22,3] float32 and smplx_world [N,79] float64: the two device tensors `frames_to_world` returns.
@@ -64,7 +74,8 @@ def build_clips(joints_world, smplx_world, clip_len, overlap_len=2, up_axis='z',
 
     Returns a dict of device tensors (float32): 'repr' [C, clip_len-1, 294], 'cano_joints' [C, clip_len, 22, 3],
     'global_orient' / 'transl' [C, clip_len, 3] (canonical; betas and body_pose pass through), 'transf_matrix'
-    [C,4,4] (scene -> canonical), and 'starts' [C] int32."""
+    [C,4,4] (scene -> canonical), and 'starts' [C] int32.  params_f64=True adds 'orient_transl64' [C, clip_len, 6]: the
+    canonical global_orient and transl in float64, as the AMASS loader keeps them; the other outputs do not change."""
     require_hip(joints_world, smplx_world)
     _check_clip_len(clip_len)
     if up_axis not in UP_AXES:
@@ -78,30 +89,61 @@ def build_clips(joints_world, smplx_world, clip_len, overlap_len=2, up_axis='z',
     if smplx_world.device != device:
         raise ValueError('joints_world and smplx_world must be on the same device')
     st, n = _windows(starts, N, clip_len, overlap_len, device)
-    mean = std = None
-    if stats is not None:
-        mean, std = (torch.as_tensor(np.asarray(s, dtype=np.float32) if not torch.is_tensor(s) else s).to(
-            device=device, dtype=torch.float32).contiguous() for s in stats)
-        if mean.shape != (294,) or std.shape != (294,):
-            raise ValueError('stats must be (Mean [294], Std [294])')
+    mean, std = _stats_tensors(stats, device)
     L = int(clip_len)
     f32 = dict(device=device, dtype=torch.float32)
     out = {'repr': torch.empty(n, L - 1, 294, **f32), 'cano_joints': torch.empty(n, L, 22, 3, **f32),
            'global_orient': torch.empty(n, L, 3, **f32), 'transl': torch.empty(n, L, 3, **f32),
            'transf_matrix': torch.empty(n, 4, 4, **f32),
            'starts': st if st is not None else torch.arange(n, device=device, dtype=torch.int32) * (L - int(overlap_len))}
+    if params_f64:
+        out['orient_transl64'] = torch.empty(n, L, 6, device=device, dtype=torch.float64)
     if n == 0:
         return out
     nbytes = lib().rohm_clips_scratch_bytes(n, L)
     scratch = torch.empty(nbytes, device=device, dtype=torch.uint8) if nbytes else None
     has_preset = preset_floor_height is not None
+    head = (ptr(joints_world.contiguous()), ptr(smplx_world.contiguous()), N, ptr(st), n, L, int(overlap_len), UP_AXES[up_axis],
+            int(has_preset), float(preset_floor_height) if has_preset else 0.0, ptr(mean), ptr(std), ptr(out['repr']),
+            ptr(out['cano_joints']), ptr(out['global_orient']), ptr(out['transl']), ptr(out['transf_matrix']))
     with torch.cuda.device(device):
-        check(lib().rohm_clips_build(ptr(joints_world.contiguous()), ptr(smplx_world.contiguous()), N, ptr(st), n, L,
-                                     int(overlap_len), UP_AXES[up_axis], int(has_preset),
-                                     float(preset_floor_height) if has_preset else 0.0, ptr(mean), ptr(std),
-                                     ptr(out['repr']), ptr(out['cano_joints']), ptr(out['global_orient']), ptr(out['transl']),
-                                     ptr(out['transf_matrix']), ptr(scratch), nbytes, stream_ptr(device)), 'rohm_clips_build')
+        if params_f64:
+            check(lib().rohm_clips_build_f64(*head, ptr(out['orient_transl64']), ptr(scratch), nbytes, stream_ptr(device)),
+                  'rohm_clips_build_f64')
+        else:
+            check(lib().rohm_clips_build(*head, ptr(scratch), nbytes, stream_ptr(device)), 'rohm_clips_build')
     return out
+
+
+def clips_repr(positions, params, stats=None, joint_noise=None, return_joints=False):
+    """`get_repr_smplx` (feet_vel_thre 5e-5) of clips that are canonical already: positions [C,L,22,3] (device float32 or
+    float64), params [C,L,79] float64 (global_orient, transl, betas, body_pose) -> [C, L-1, 294] float32.  The arithmetic
+    the reference does in the joints' dtype follows the dtype of `positions`.  joint_noise [C,L,22,3] float64: the joints
+    become float32(positions + joint_noise) first (the sep_noise items of the AMASS loader); return_joints=True also
+    returns the float32 joints the representation was made of."""
+    require_hip(positions, params, joint_noise)
+    if positions.dim() != 4 or positions.shape[2:] != (22, 3) or positions.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f'positions must be float32 / float64 [C,L,22,3], got {positions.dtype} {tuple(positions.shape)}')
+    n, L = int(positions.shape[0]), int(positions.shape[1])
+    _check_clip_len(L)
+    device = positions.device
+    if params.shape != (n, L, 79) or params.dtype != torch.float64 or params.device != device:
+        raise ValueError(f'params must be float64 [{n},{L},79] on {device}, got {params.dtype} {tuple(params.shape)}')
+    if joint_noise is not None and (joint_noise.shape != positions.shape or joint_noise.dtype != torch.float64 or
+                                    joint_noise.device != device):
+        raise ValueError(f'joint_noise must be float64 {tuple(positions.shape)} on {device}')
+    mean, std = _stats_tensors(stats, device)
+    out = torch.empty(n, L - 1, 294, device=device, dtype=torch.float32)
+    joints = torch.empty(n, L, 22, 3, device=device, dtype=torch.float32) if return_joints else None
+    if n:
+        nbytes = lib().rohm_clips_scratch_bytes(n, L)
+        scratch = torch.empty(nbytes, device=device, dtype=torch.uint8) if nbytes else None
+        with torch.cuda.device(device):
+            check(lib().rohm_clips_repr(ptr(positions.contiguous()), int(positions.dtype == torch.float64), ptr(params.contiguous()),
+                                        ptr(joint_noise.contiguous() if joint_noise is not None else None), n, L, ptr(mean),
+                                        ptr(std), ptr(out), ptr(joints), ptr(scratch), nbytes, stream_ptr(device)),
+                  'rohm_clips_repr')
+    return (out, joints) if return_joints else out
 
 
 def undistort_keypoints(keypoints, camera_mtx, dist_coeffs, image_width=1920):

@@ -5,7 +5,8 @@ they read a recording (plus a cam2world transform and `update_globalRT_for_smplx
 `data_loaders/dataloader_amass.py:194-206` calls it once per clip on the noise-perturbed parameters.  These two
 functions take the arrays the loaders hold at those lines and return what those lines produce, for all frames in one
 launch.  The test-time loader around the first one is `dataloader_video.DataloaderVideo` (files read on the host, clips
-built by `clips.build_clips` from what `frames_to_world` returns); the AMASS training loader stays the reference's."""
+built by `clips.build_clips` from what `frames_to_world` returns); the AMASS loader around the second one is
+`dataloader_amass.DataloaderAMASS`, which calls it once per chunk of clips."""
 from __future__ import annotations
 
 import numpy as np
