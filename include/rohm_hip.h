@@ -775,6 +775,34 @@ int rohm_image_overlay(const unsigned char* dst_rgb, const unsigned char* src_rg
 int rohm_image_flip_lr(const unsigned char* in, long long rows, int W, int channels, unsigned char* out,
                        rohm_stream_t stream);
 
+/* The condition masks of the training loops (csrc/train_masks.hip).  The loop decides on the host what to hide; the device
+ * applies it.  Device pointers unless stated, the caller's stream, never synchronised, nothing allocated.
+ *
+ * rohm_train_cond: PoseNet's training condition of a batch, training_loop_posenet.py:107-205 (and :221-248 of the eval block), in
+ * one launch.  src [B, T, 294] float32 (the batch's normalised motion_repr_noisy or motion_repr_clean rows) ->
+ * cond [B, 294, 1, T]; with clean [B, T, 294] also clean_t [B, 294, 1, T] = clean transposed, bit for bit (the loop's two
+ * permute(0, 2, 1).unsqueeze(-2) copies).  1 <= T <= 512.  Per item, each NULL or present:
+ *   joint_bits [B] uint32   bit j set: joint j is hidden in every frame (stored as 0).
+ *   window [B, 2] int32     (start, end): frames start <= f < end lose every channel from 22 on (stored as 0).
+ *   vis_bits [n_vis, vis_rows] uint32 with vis_index [B] int64: bit j of row f of clip vis_index[b] set: joint j is visible
+ *                           at frame f; the value is MULTIPLIED by the 0 / 1 mask, as the PROX branch does (:157).  Rows
+ *                           0 .. T-1 of a clip are used (vis_rows >= T).  vis_index_host, when not NULL, is a HOST copy of
+ *                           vis_index that is range-checked before the launch; on the device an index outside [0, n_vis)
+ *                           reads nothing and gives NaN rows.
+ * zero_contact != 0 stores 0 in the four contact channels.  Channels in REPR_LIST order: 0..21 trajectory, never masked;
+ * 22..87 local positions, joint (c-22)/3; 88..153 local velocities, joint (c-88)/3; 154..279 body pose 6d, joint
+ * 1 + (c-154)/6; 280..289 betas, never masked by joints; 290, 291 left and 292, 293 right foot contact: hidden with
+ * joint_bits when bit 7 or 10 (left) / 8 or 11 (right) is set, visible with vis_bits only when joints 7 and 10 (left) / 8 and
+ * 11 (right) are both visible.  The multiplication comes first, then the stores of 0.  The outputs must not alias the inputs.
+ * Errors before any launch (ROHM_ERR_ARG): B < 0, T outside [1, 512], vis_rows < T, a vis_index_host entry outside [0, n_vis).
+ *
+ * rohm_train_traj_window: training_loop_trajnet.py:72-82 in place on cond [B, T, C]: the first n_ch channels of frames
+ * window[b][0] <= t < window[b][1] (window [B, 2] int32) are multiplied by 0, everything else by 1 (left as it is). */
+int rohm_train_cond(const float* src, const float* clean, int B, int T, const unsigned* joint_bits, const int* window,
+                    const unsigned* vis_bits, int n_vis, int vis_rows, const long long* vis_index,
+                    const long long* vis_index_host, int zero_contact, float* cond, float* clean_t, rohm_stream_t stream);
+int rohm_train_traj_window(float* cond, int B, int T, int C, int n_ch, const int* window, rohm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
