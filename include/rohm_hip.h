@@ -803,6 +803,40 @@ int rohm_train_cond(const float* src, const float* clean, int B, int T, const un
                     const long long* vis_index_host, int zero_contact, float* cond, float* clean_t, rohm_stream_t stream);
 int rohm_train_traj_window(float* cond, int B, int T, int C, int n_ch, const int* window, rohm_stream_t stream);
 
+/* The optimiser step of the training loops (csrc/optim.hip): train/training_loop_posenet.py:52-54,278 and
+ * train/training_loop_trajnet.py hold a torch.optim.AdamW and call its step(); the reference has no gradient clipping.
+ * The tables (params, grads, exp_avg, exp_avg_sq, numel) are HOST arrays of n_tensors entries whose pointer entries are DEVICE
+ * pointers to contiguous fp32 (4-byte aligned; they need not be 16-byte aligned: a parameter may be a view into a larger
+ * buffer).  The library copies the entries into the kernel arguments before it returns, so the caller may rewrite or free the
+ * arrays at once, and gradient pointers may differ from step to step.  Tensors of 0 elements are skipped.  The caller's stream,
+ * never synchronised, nothing allocated, no atomics.
+ *
+ * rohm_adamw_step: one AdamW update of every listed tensor with the same hyper-parameters and the same step count `step` (>= 1,
+ * the count AFTER this step, as torch's state['step']): torch.optim.AdamW with decoupled weight decay and without amsgrad,
+ * in the operation order of torch/optim/adam.py _single_tensor_adam (non-capturable branch).  The scalars are derived in double
+ * and converted to float once: decay = 1 - lr weight_decay, w1 = 1 - beta1, w2 = 1 - beta2, bc2_sqrt = sqrt(1 - beta2^step),
+ * step_size = lr / (1 - beta1^step).  Per element in fp32:
+ *     p *= decay                       (skipped when weight_decay == 0)
+ *     g' = g * *clip_coef              (skipped when clip_coef is NULL)
+ *     m += w1 (g' - m);   v = v beta2 + w2 g' g';   p -= step_size m / (sqrt(v) / bc2_sqrt + eps)
+ * clip_coef, when not NULL, is a device pointer to one float, typically out + 1 of rohm_grad_norm on the same stream.  The
+ * gradients themselves are only read: unlike torch.nn.utils.clip_grad_norm_, clipping does NOT rescale the stored gradients.
+ * beta1 must exceed 0.5 (torch's lerp takes another form below that).  Launches: one per rohm_adamw_limits' tensors_per_launch
+ * tensors; a tensor is cut into blocks of elems_per_block elements.
+ *
+ * rohm_grad_norm: out[0] = the L2 norm over all listed gradients, out[1] = min(1, max_norm / (out[0] + 1e-6)), the coefficient
+ * of torch.nn.utils.clip_grad_norm_ (error_if_nonfinite=False: a NaN norm gives a NaN coefficient, an infinite norm 0; nothing
+ * is raised).  out: device, 2 floats, 8-byte aligned.  Squares are summed in double, per block into `scratch`
+ * (rohm_grad_norm_scratch_bytes for the total element count and the tensor count; 8-byte aligned), then by one finishing
+ * block in slot order: the same inputs give the same bits on every call.  ROHM_ERR_WORKSPACE when scratch is too small. */
+int rohm_adamw_limits(int* tensors_per_launch, int* elems_per_block);
+int rohm_adamw_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                    const long long* numel, int n_tensors, double lr, double beta1, double beta2, double eps,
+                    double weight_decay, long long step, const float* clip_coef, rohm_stream_t stream);
+size_t rohm_grad_norm_scratch_bytes(long long total_elems, int n_tensors);
+int rohm_grad_norm(const float* const* grads, const long long* numel, int n_tensors, float max_norm, float* out,
+                   void* scratch, size_t scratch_bytes, rohm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

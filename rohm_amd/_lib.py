@@ -216,6 +216,12 @@ SIGNATURES = {
     'rohm_train_cond': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                   C.c_void_p, c_int64_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rohm_train_traj_window': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'rohm_adamw_limits': (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'rohm_adamw_step': (C.c_int, [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(C.c_longlong), C.c_int] + [C.c_double] * 5 +
+                        [C.c_longlong, C.c_void_p, C.c_void_p]),
+    'rohm_grad_norm_scratch_bytes': (C.c_size_t, [C.c_longlong, C.c_int]),
+    'rohm_grad_norm': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                 C.c_size_t, C.c_void_p]),
 }
 
 

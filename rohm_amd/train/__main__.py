@@ -3,8 +3,10 @@ train_trajnet.py on the native loader, models, losses and loops.
 
 The arguments and their defaults are those of train_posenet.py:26-69 and train_trajnet.py:28-76.  A config file is the flat
 `key: value  # comment` text of cfg_files/train_cfg/*.yaml, read by `read_config` (no configargparse, no PyYAML); command-line
-values override it.  Out of scope, as in the rest of the package's training path: an optimiser kernel, mixed precision,
-multi-GPU training, and the shuffle order or hidden seed draws of the reference's DataLoader.
+values override it.  Two arguments are the package's own: `--optimizer torch|native` (default torch: torch.optim.AdamW as the
+reference; native: rohm_amd.optim.AdamW, one fused HIP pass over all parameters) and `--max_grad_norm X` (default none; native
+only: clip the global gradient norm on the device).  Out of scope, as in the rest of the package's training path: mixed
+precision, multi-GPU training, and the shuffle order or hidden seed draws of the reference's DataLoader.
 """
 from __future__ import annotations
 
@@ -17,6 +19,8 @@ import sys
 import torch
 
 _bool = lambda x: str(x).lower() in ['true', '1']      # noqa: E731  (the drivers' own rule)
+_opt_float = lambda x: None if str(x).lower() in ['none', ''] else float(x)      # noqa: E731
+
 
 COMMON = [
     ('device', 0, int),
@@ -28,6 +32,7 @@ COMMON = [
     ('noise_std_smplx_betas', 0.2, float),
     ('debug', False, _bool), ('save_dir', 'runs', str), ('lr', 1e-4, float), ('weight_decay', 0.0, float),
     ('log_interval', 25000, int), ('save_interval', 25000, int), ('num_steps', 1000000_000, int),
+    ('optimizer', 'torch', str), ('max_grad_norm', None, _opt_float),
 ]
 POSENET = COMMON + [
     ('diffusion_steps', 1000, int), ('task', 'pose', str), ('noise_std_smplx_trans', 0.01, float),
@@ -48,7 +53,7 @@ TRAJNET = COMMON + [
     ('start_infill_epoch', 100000000000000000000, int),
 ]
 SPECS = {'posenet': POSENET, 'trajnet': TRAJNET}
-CHOICES = {'noise_schedule': ['linear', 'cosine'], 'task': ['traj', 'pose'],
+CHOICES = {'noise_schedule': ['linear', 'cosine'], 'task': ['traj', 'pose'], 'optimizer': ['torch', 'native'],
            'mask_scheme': ['lower', 'lower+upper', 'lower+full', 'lower+upper+full']}
 TRAIN_DATASETS = ['HumanEva', 'HDM05', 'MoSh', 'Transitions', 'ACCAD', 'BMLhandball', 'BMLmovi', 'BMLrub', 'CMU', 'DFaust',
                   'Eyes_Japan_Dataset', 'PosePrior', 'SSM', 'GRAB', 'SOMA']
@@ -106,7 +111,10 @@ def parse_args(which, argv):
             if k in CHOICES and v not in CHOICES[k]:
                 raise ValueError(f'{known.config}: {k} must be one of {CHOICES[k]}, got {v!r}')
         parser.set_defaults(**values)
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    if args.max_grad_norm is not None and args.optimizer != 'native':
+        raise ValueError("max_grad_norm needs optimizer = native: the torch optimiser of the loops does not clip")
+    return args
 
 
 def prepare_trajcontrol(model, backbone_state_dict=None):

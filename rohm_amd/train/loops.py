@@ -1,5 +1,7 @@
 """RoHM's training loops (train/training_loop_posenet.py, train/training_loop_trajnet.py) on the native pieces: device batches,
-the mask schedules of `rohm_amd.train.masks`, the native `training_losses`, torch's AdamW.
+the mask schedules of `rohm_amd.train.masks`, the native `training_losses`, and AdamW: torch's by default, or the native
+`rohm_amd.optim.AdamW` (one fused pass, optional gradient-norm clipping on the device) with `args.optimizer = 'native'` and
+`args.max_grad_norm`.
 
 The classes keep the reference's constructor arguments and methods (`run_loop`, `run_step`, `forward_backward`, `save`,
 `ckpt_file_name`).  A loader is either a `DataloaderAMASS`, iterated with `batches()`, or any iterable of dict batches that has
@@ -77,9 +79,23 @@ class _TrainLoop:
         self.num_steps = args.num_steps
         self.num_epochs = self.num_steps // len(self.train_dataloader) + 1
         self.save_dir, self.logger = logdir, logger
-        self.opt = AdamW([p for p in self.model.parameters() if p.requires_grad], lr=self.lr, weight_decay=self.weight_decay)
+        self.opt = self._make_optimizer([p for p in self.model.parameters() if p.requires_grad])
         # UniformSampler (diffusion/resample.py): every timestep has weight 1
         self._p = np.ones([diffusion_train.num_timesteps]) / diffusion_train.num_timesteps
+
+    def _make_optimizer(self, params):
+        """args.optimizer: 'torch' (the default: torch.optim.AdamW, as the reference) or 'native' (rohm_amd.optim.AdamW);
+        args.max_grad_norm: clip the global gradient norm, native only."""
+        kind = getattr(self.args, 'optimizer', 'torch')
+        max_grad_norm = getattr(self.args, 'max_grad_norm', None)
+        if kind == 'torch':
+            if max_grad_norm is not None:
+                raise ValueError("max_grad_norm needs optimizer='native': the torch optimiser of the loop does not clip")
+            return AdamW(params, lr=self.lr, weight_decay=self.weight_decay)
+        if kind != 'native':
+            raise ValueError(f"optimizer must be 'torch' or 'native', got {kind!r}")
+        from ..optim import AdamW as NativeAdamW
+        return NativeAdamW(params, lr=self.lr, weight_decay=self.weight_decay, max_grad_norm=max_grad_norm)
 
     # -- the pieces of a step ----------------------------------------------------------------------------------------------------
     def sample_timesteps(self, batch_size):

@@ -10,9 +10,10 @@
 Both sides produce the same bits (checked before timing).  They are warmed up, then alternate in windows of about 0.1 s that end in a device
 synchronise until each side has at least --min-seconds.  A whole PoseNet training step (mask block + training_losses + backward +
 AdamW) is timed the same way for the mask block's share; the native training path takes T <= 143, so the step runs at
---step-T (143).  Writes profiles/train_loop_timing.json.  Needs the GPU: there is no CPU fallback and no number without a run.
+--step-T (143); --optimizer native runs that step with rohm_amd.optim.AdamW instead of torch.optim.AdamW (the default, and what
+the loops use unless asked) and adds the two optimisers' whole steps alternating.  Writes profiles/train_loop_timing.json.  Needs the GPU: there is no CPU fallback and no number without a run.
 
-    python scripts/bench_train_loop.py [--B 64] [--T 144] [--min-seconds 1.0] [--prox-clips 500]
+    python scripts/bench_train_loop.py [--B 64] [--T 144] [--min-seconds 1.0] [--prox-clips 500] [--optimizer torch|native]
 """
 import argparse
 import json
@@ -74,7 +75,7 @@ def indexed_block(d, src, clean, prox_host, input_noise):
 
 
 def alternate(sides, min_seconds, window=0.1):
-    """{name: fn} -> {name: (ms per call, calls)}: the sides take turns in windows of about `window` seconds each (the calls per
+    """{name: fn} -> {name: (ms per call, calls, least window's ms per call, greatest window's)}: the sides take turns in windows of about `window` seconds each (the calls per
     window are sized per side from one timed call, so a slow side does not stretch the run), every window closed by a
     synchronise, until each side has at least min_seconds."""
     chunk = {}
@@ -86,16 +87,18 @@ def alternate(sides, min_seconds, window=0.1):
         fn()
         torch.cuda.synchronize()
         chunk[name] = max(1, min(1000, int(window / max(time.perf_counter() - t0, 1e-6))))
-    total, calls = {k: 0.0 for k in sides}, {k: 0 for k in sides}
+    total, calls, per_window = {k: 0.0 for k in sides}, {k: 0 for k in sides}, {k: [] for k in sides}
     while min(total.values()) < min_seconds:
         for name, fn in sides.items():
             t0 = time.perf_counter()
             for _ in range(chunk[name]):
                 fn()
             torch.cuda.synchronize()
-            total[name] += time.perf_counter() - t0
+            dt = time.perf_counter() - t0
+            total[name] += dt
             calls[name] += chunk[name]
-    return {k: (total[k] * 1e3 / calls[k], calls[k]) for k in sides}
+            per_window[name].append(dt * 1e3 / chunk[name])
+    return {k: (total[k] * 1e3 / calls[k], calls[k], min(per_window[k]), max(per_window[k])) for k in sides}
 
 
 def decisions(B, T, bank):
@@ -117,6 +120,7 @@ def main():
     ap.add_argument('--step-T', type=int, default=143)
     ap.add_argument('--min-seconds', type=float, default=1.0)
     ap.add_argument('--prox-clips', type=int, default=500)
+    ap.add_argument('--optimizer', choices=['torch', 'native'], default='torch')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'train_loop_timing.json'))
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -177,13 +181,18 @@ def main():
     net.load_state_dict(synth.posenet_state_dict(0), strict=False)
     net = net.to(dev).train()
     diff = create_gaussian_diffusion(Args, gdp, SpacedDiffusionPoseNet, 1000, '', device=dev)
-    opt = torch.optim.AdamW([p for p in net.parameters() if p.requires_grad], lr=1e-4)
+    from rohm_amd.optim import AdamW as NativeAdamW
+    trainable = [p for p in net.parameters() if p.requires_grad]
+    opts = {'torch': torch.optim.AdamW(trainable, lr=1e-4)}
+    if a.optimizer == 'native':
+        opts['native'] = NativeAdamW(trainable, lr=1e-4)
+    opt = opts[a.optimizer]
     rows = synth.plausible_motion(3, B, Ts, DS.Mean, DS.Std)[:, :, 0].permute(0, 2, 1).contiguous().to(dev)
     noisy = (rows + 0.05 * torch.randn_like(rows)).contiguous()
     bank_s = M.ProxMaskBank(masks=[masks[0][:a.prox_clips * (Ts + 1)]], clip_len=Ts + 1, device=dev)
     sched_s = M.PoseMaskSchedule(0, 'lower+upper+full', True, bank_s)
 
-    def step(with_masks):
+    def step(with_masks, opt=opt):
         batch = {'motion_repr_clean': rows, 'motion_repr_noisy': noisy}
         if with_masks:
             sched_s(batch, 1)
@@ -198,8 +207,17 @@ def main():
     t = alternate({'step': lambda: step(True), 'step_without_mask_block': lambda: step(False)}, a.min_seconds)
     result['posenet_step'] = {'T': Ts, 'layers': 8, 'step_ms': t['step'][0], 'step_without_mask_block_ms': t['step_without_mask_block'][0],
                               'calls': t['step'][1]}
+    result['posenet_step']['optimizer'] = a.optimizer
     print(f"PoseNet step at T = {Ts}: {t['step'][0]:.3f} ms with the mask block, {t['step_without_mask_block'][0]:.3f} ms without",
           flush=True)
+    if a.optimizer == 'native':
+        # The same whole step under each optimiser, taking turns.  Both step the SAME parameter tensors, each with its own
+        # moments: fine for a timing (the work per step does not depend on the values), meaningless as a training run.
+        t = alternate({k: (lambda o=o: step(True, o)) for k, o in opts.items()}, a.min_seconds)
+        result['posenet_step_by_optimizer'] = {k: {'step_ms': v[0], 'calls': v[1], 'window_ms_min': v[2], 'window_ms_max': v[3]}
+                                               for k, v in t.items()}
+        print('PoseNet step by optimiser: ' + ', '.join(f'{k} {v[0]:.3f} ms [{v[2]:.3f}, {v[3]:.3f}]' for k, v in t.items()),
+              flush=True)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, 'w') as f:
         json.dump(result, f, indent=1)
