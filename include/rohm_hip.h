@@ -310,7 +310,7 @@ int rohm_posenet_sample_loop(const rohm_posenet_t* h, float* x, const float* con
  * train/training_loop_posenet.py: the train-mode forward of PoseNet (model/posenet.py:75-96 with the five dropouts of
  * model/heads.py:126-129 and nn.TransformerEncoderLayer) and its backward.  No handle: `w` holds device pointers to the LIVE
  * parameters on every call (an optimiser step needs no rebuild).  Shapes: d_model 512, 4 heads, d_ff 1024, any n_layer >= 1,
- * c_out + traj_dim == c_in, 1 <= B <= 16383, 1 <= T <= 143; anything else returns ROHM_ERR_UNSUPPORTED (rohm_last_error names
+ * c_out + traj_dim == c_in, 1 <= B <= 16383, 1 <= T <= 144; anything else returns ROHM_ERR_UNSUPPORTED (rohm_last_error names
  * the shape).  Exact fp32 (fp32 MFMA), no atomics (bitwise reproducible), no host synchronisation.
  * Dropout (keep-scale 1 / (1 - p), 0 <= p < 1): element e of site s of layer l is kept iff a counter-based hash of (seed, 8 l + s, e)
  * falls below (1 - p) 2^32.  Sites and the flat shapes their e indexes: 0 the PositionalEncoding dropout on the token sequence
@@ -836,6 +836,45 @@ int rohm_adamw_step(float* const* params, const float* const* grads, float* cons
 size_t rohm_grad_norm_scratch_bytes(long long total_elems, int n_tensors);
 int rohm_grad_norm(const float* const* grads, const long long* numel, int n_tensors, float max_norm, float* out,
                    void* scratch, size_t scratch_bytes, rohm_stream_t stream);
+
+/* The result tails of the test drivers (csrc/results.hip).
+ *
+ * rohm_result_rows de-normalises up to ROHM_RESULT_ROWS_MAX representations in one launch (test_amass_full.py:387-396 and
+ * the same lines of the other drivers): out[b, t, c] = src[b stride_b + t stride_t + c stride_c] * std[c] + mean[c] for
+ * b < B, t < T, c < C, as a rounded float32 product followed by a rounded float32 sum (numpy's two operations: the result
+ * equals the scripts' bit for bit).  Strides are in elements; either the frames (stride_t == 1: the samplers'
+ * [B, C, 1, T] output) or the channels (stride_c == 1: the first T rows of a [B, T', C] tensor) must be contiguous.
+ * traj, when not NULL, is a contiguous [B, traj_rows, 22] tensor (traj_rows >= T, C >= 22) whose rows replace channels
+ * 0..21 BEFORE de-normalisation (`motion_repr_noisy[:, :, 0:22] = traj_noisy_full[:, 0:-1, :]`, test_amass_full.py:391).
+ * out is contiguous [B, T, C] and must not overlap a source.  `items` is read on the host during the call.  Errors before
+ * any launch (ROHM_ERR_ARG): a null pointer, n_items outside [1, ROHM_RESULT_ROWS_MAX], traj_rows < T, neither axis
+ * contiguous, B * n_items > 65535.
+ *
+ * rohm_traj_report: the report of test_trajnet.py:221-263, :333-366 as per-clip sums, one wave per clip, no atomics (lanes
+ * stride over frames, accumulate in double, one butterfly reduction: the same bits on every call).  The five joint tensors
+ * are contiguous [B, T, 22, 3]; only joint 0 (the pelvis) is read.  rot_clean / rot_rec point at channel 0 of the
+ * de-normalised clean / reconstructed representation of clip 0, frame (b, t) at [(b T + t) stride].  out [B, 15] doubles:
+ *   0        sum_t |2 rot_rec - 2 rot_clean|                                                          (of T)
+ *   1 + 3r+x sum_t |pelvis_r[t, x] - pelvis_clean[t, x]|, r = 0 from_abs_traj, 1 from_rel_traj, 2 from_smpl   (of T)
+ *   10 + k   sum_t ||(p[t+3] - 3 p[t+2] + 3 p[t+1] - p[t]) * 30^3||, k = clean, noisy, from_abs_traj, from_rel_traj, from_smpl
+ *            (of T - 3), every operation a rounded float32 one in numpy's order, the square root correctly rounded
+ * elems, when not NULL, receives the float32 terms of these sums as [B, 15, T] (rows 10..14: frames >= T - 3 are 0).
+ * T < 4 is ROHM_ERR_ARG. */
+#define ROHM_RESULT_ROWS_MAX 3
+typedef struct {
+    const float* src;
+    long long stride_b, stride_t, stride_c;
+    const float* mean;
+    const float* std;
+    const float* traj;
+    long long traj_rows;
+    float* out;
+} rohm_result_rows_item;
+int rohm_result_rows(const rohm_result_rows_item* items, int n_items, int B, int T, int C, rohm_stream_t stream);
+int rohm_traj_report(const float* joints_clean, const float* joints_noisy, const float* joints_from_abs_traj,
+                     const float* joints_from_rel_traj, const float* joints_from_smpl, const float* rot_clean,
+                     long long rot_clean_stride, const float* rot_rec, long long rot_rec_stride, int B, int T,
+                     double* out, float* elems, rohm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,11 @@ class TrajNetWeights(C.Structure):
     _fields_ = [('tensors', C.POINTER(TensorRef)), ('n_tensors', C.c_int)]
 
 
+class ResultRowsItem(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('stride_b', C.c_longlong), ('stride_t', C.c_longlong), ('stride_c', C.c_longlong),
+                ('mean', C.c_void_p), ('std', C.c_void_p), ('traj', C.c_void_p), ('traj_rows', C.c_longlong), ('out', C.c_void_p)]
+
+
 class ProfileRow(C.Structure):
     _fields_ = [('name', C.c_char * 48), ('launches', C.c_uint64), ('total_ms', C.c_double),
                 ('flops', C.c_double), ('bytes', C.c_double)]
@@ -222,6 +227,9 @@ SIGNATURES = {
     'rohm_grad_norm_scratch_bytes': (C.c_size_t, [C.c_longlong, C.c_int]),
     'rohm_grad_norm': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                  C.c_size_t, C.c_void_p]),
+    'rohm_result_rows': (C.c_int, [C.POINTER(ResultRowsItem), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'rohm_traj_report': (C.c_int, [C.c_void_p] * 6 + [C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p]),
 }
 
 

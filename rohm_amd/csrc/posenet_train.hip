@@ -7,7 +7,7 @@
 // library).  Its operands are addressed through (row, column, batch) strides, so the transposed operands of the backward -- the
 // reduction axis of a weight gradient is the token axis, the attention's dK / dV contract over queries -- are staged through LDS
 // transposed instead of being materialised, and the [B, C, 1, T] channel-major tensors of the embeds and the output head are read
-// and written in place.  Weight gradients split their token axis into slices of kRowsPerSplit rows (whole clips) that go to their own
+// and written in place.  Weight gradients split their token axis into slices of kRowsPerSplit rows that go to their own
 // partial slab, and a second kernel adds the slabs in index order: no float atomics anywhere, so every gradient is bitwise reproducible.
 //
 // Dropout (train mode, keep-scale 1 / (1 - p)) at the reference's five sites: 0 PositionalEncoding (model/heads.py:126-129) on the
@@ -23,8 +23,9 @@ namespace {
 
 #include "train_reduce.h"
 
-constexpr int kD = 512, kH = 4, kF = 1024, kDh = 128, kMaxS = 144;
-constexpr int kRowsPerSplit = 576;      // token rows per weight-gradient slice (4 clips of 144)
+constexpr int kD = 512, kH = 4, kF = 1024, kDh = 128, kMaxS = 145;
+constexpr int kRowsPerSplit = 576;      // token rows per weight-gradient slice: 4 clips of 144 tokens, but any M goes -- a slice may cut a
+                                        // clip (S = 145), and the last one is short: tgemm_kernel's k_total remainder bounds its K loop
 
 // ---------------------------------------------------------------------------------------------------------------- dropout
 __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
@@ -255,7 +256,7 @@ __device__ __forceinline__ float wave_max64(float v) {
     return v;
 }
 
-// Softmax over the S <= 144 keys of a row (one wave per row): P (saved) and, when the dropout is on, Pd = dropout(P).
+// Softmax over the S <= 145 keys (three 64-key chunks: up to 192) of a row (one wave per row): P (saved) and, when the dropout is on, Pd = dropout(P).
 __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float* sc, float* P, float* __restrict__ Pd,
                                                           Drop drop, int rows, int S) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -461,7 +462,7 @@ int check_dims(int d_model, int n_head, int d_ff, int n_layer, int c_in, int c_o
     if (d_model != kD || n_head != kH || d_ff != kF || n_layer < 1 || c_in < 1 || c_out < 1 || traj < 0 || c_out + traj != c_in ||
         B < 1 || B > 16383 || T < 1 || T + 1 > kMaxS) {
         set_error("posenet training: unsupported shape d_model=%d n_head=%d d_ff=%d n_layer=%d c_in=%d c_out=%d traj=%d B=%d T=%d "
-                  "(supported: d_model 512, 4 heads, d_ff 1024, n_layer >= 1, c_out + traj == c_in, 1 <= B <= 16383, 1 <= T <= 143)",
+                  "(supported: d_model 512, 4 heads, d_ff 1024, n_layer >= 1, c_out + traj == c_in, 1 <= B <= 16383, 1 <= T <= 144)",
                   d_model, n_head, d_ff, n_layer, c_in, c_out, traj, B, T);
         return ROHM_ERR_UNSUPPORTED;
     }

@@ -210,6 +210,9 @@ class DataloaderVideo(data.Dataset):
         read = read_prox_recording if dataset == 'prox' else read_egobody_recording
         rec = read(init_root, base_dir, recording_name, joints_num)
         self.scene_name, self.color_cam = rec['scene_name'], rec['color_cam']
+        # dataloader_video.py:102-104, :252-254: what PoseNet's 2-D guidance reads of its dataset (posenet.py:296)
+        cam2world = torch.from_numpy(np.asarray(rec['cam2world'], dtype=np.float64)).float().to(self.device)
+        self.cam_R, self.cam_t = cam2world[:3, :3].reshape([3, 3]), cam2world[:3, 3].reshape([1, 3])
         if dataset == 'egobody':
             self.view, self.body_idx, self.gender_gt = rec['view'], rec['body_idx'], rec['gender_gt']
             self.fitting_gt_root = rec['fitting_gt_root']
@@ -268,7 +271,7 @@ class DataloaderVideo(data.Dataset):
     def __getstate__(self):
         # what a DataLoader worker gets (spawn / forkserver): the host items only, nothing that lives on the device
         return {k: v for k, v in self.__dict__.items()
-                if k not in ('_device_data', 'smplx_neutral') and not k.startswith('_rohm_stats_')}
+                if k not in ('_device_data', 'smplx_neutral', 'cam_R', 'cam_t') and not k.startswith('_rohm_stats_')}
 
     def __len__(self):
         return self.n_samples
