@@ -617,6 +617,21 @@ int rohm_amass_batch(const float* repr_clean, const float* repr_noisy, long long
                      int noisy_per_batch, int cond_kind, float* out_clean, float* out_noisy, float* cond, float* control_cond,
                      rohm_stream_t stream);
 
+/* The per-frame work of preprocessing_amass.py:47-69 for N frames of R recordings that lie back to back (all device pointers):
+ * every input is cast float64 -> float32 with round-to-nearest-even, as torch.Tensor(ndarray) does (:48-55); params [N,178] is
+ * the row of :68 -- root_orient 3, trans 3, betas 10, pose_body 63, pose_hand 90, pose_jaw 3, pose_eye[:, 0:3] and
+ * pose_eye[:, 0:3] AGAIN (:54-55 read the left eye twice; the script's comment says 169, the row has 178 columns) -- and
+ * joints [N,25,3] is smplx_output.joints[:, 0:25] of :65-66 in float32 from the cast values: Rodrigues (angle = |r + 1e-8|) and
+ * the chain of rohm_smplx_joints for joints 0..21, P[j] = P[p] + G[p] (Jrest[j] - Jrest[p]), p = parents[j], for the leaves
+ * 22..24 (jaw, eyes), plus trans.  Those joints depend on betas, root_orient, pose_body and trans only (hand_pose is no argument
+ * of SMPLX.forward, and the jaw / eye rotations turn nothing that is read), so no vertices are computed.  betas [R,10] holds
+ * bdata['betas'][:10] of each recording (:50); rec_of_frame [N] in [0, R) picks a frame's row (a value outside gives NaN betas).
+ * The handle needs J >= 25 and parents[22..24] among the 22 body joints (argument error otherwise).  Runs on `stream` without
+ * synchronising; N == 0 returns without a launch. */
+int rohm_amass_preprocess(const rohm_smplx_t* h, const double* root_orient, const double* trans, const double* pose_body,
+                          const double* pose_hand, const double* pose_jaw, const double* pose_eye, const double* betas,
+                          const int32_t* rec_of_frame, int N, int R, float* joints, float* params, rohm_stream_t stream);
+
 /* dataloader_video.py:441-458 for M keypoints [M,3] (x, y, confidence; device float32): x -> image_width - 1 - x,
  * cv2.undistortPoints(src, camera_mtx, dist, P = camera_mtx) (five fixed-point iterations of the inverse of the
  * k1 k2 p1 p2 k3 model), x flipped back; the confidence passes through.  camera_mtx9 (row-major 3x3) and dist5 are HOST

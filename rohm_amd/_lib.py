@@ -195,6 +195,7 @@ SIGNATURES = {
     'rohm_repr_stats': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'rohm_amass_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    'rohm_amass_preprocess': (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rohm_keypoints_undistort': (C.c_int, [C.c_void_p, C.c_longlong, c_double_p, c_double_p, C.c_double, C.c_void_p,
                                            C.c_void_p]),
     'rohm_visibility_masks': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,

@@ -4,7 +4,9 @@
 //     plain additive noise of the sep_noise items (:298-303), float64 throughout like the reference's numpy / scipy;
 //   * rohm_repr_stats: per-channel mean and population std of the clean representation (:254-258), float64 accumulation
 //     in two deterministic stages;
-//   * rohm_amass_batch: the item assembly of __getitem__ (:317-339) for a vector of item indices.
+//   * rohm_amass_batch: the item assembly of __getitem__ (:317-339) for a vector of item indices;
+//   * rohm_amass_preprocess: the per-frame work of preprocessing_amass.py:47-69 (float32 cast, the 178-column parameter row
+//     and joints 0..24 by joints-only FK) for the frames of many recordings in one launch.
 // No float atomics anywhere: results are bitwise reproducible.
 #include "common.h"
 #include "rot_priv.h"
@@ -146,6 +148,120 @@ static int stat_groups(long long rows, long long* per) {
     return (int)((rows + p - 1) / p);
 }
 
+// ---- raw AMASS -> the 30 fps trees (preprocessing_amass.py:47-69) -----------------------------------------------------
+constexpr int kRawCols = 178;                  // root_orient 3, trans 3, betas 10, pose_body 63, pose_hand 90, pose_jaw 3, eye 3, eye 3
+constexpr int kRawJoints = 25;                 // 22 body joints + jaw, left eye, right eye (leaves: positions from the parent's transform)
+constexpr int kRawFrames = 128;                // frames per workgroup = one lane each for the FK
+
+struct RawArgs {
+    const double *root_orient, *trans, *pose_body, *pose_hand, *pose_jaw, *pose_eye, *betas;
+    const int32_t* rec_of_frame;
+    int N, R;
+    const float *Jt, *Js;
+    const int* parents;
+    float *joints, *params;
+};
+
+// The eight runs of columns of a parameter row: source array, its row length, the run's first column (both eye runs are
+// pose_eye[:, 0:3], preprocessing_amass.py:54-55).  Kept in LDS and indexed per element, so that the copy loop has no branch
+// between its loads.
+typedef const double __attribute__((address_space(1))) * RawPtr;      // still a global-memory pointer after a trip through LDS
+struct RawSeg { RawPtr base; int width, col0; };
+
+__device__ __forceinline__ void raw_segments(const RawArgs& a, RawSeg* s) {
+    s[0] = {(RawPtr)a.root_orient, 3, 0};
+    s[1] = {(RawPtr)a.trans, 3, 3};
+    s[2] = {(RawPtr)a.betas, NBETA, 6};
+    s[3] = {(RawPtr)a.pose_body, 63, 16};
+    s[4] = {(RawPtr)a.pose_hand, 90, 79};
+    s[5] = {(RawPtr)a.pose_jaw, 3, 169};
+    s[6] = {(RawPtr)a.pose_eye, 6, 172};
+    s[7] = {(RawPtr)a.pose_eye, 6, 175};
+}
+
+// Address of column c of the parameter row of frame n, whose recording is `rec`.  An index outside [0, R) reads betas[0] and is
+// replaced by NaN afterwards (`bad`): never a read outside the arrays.
+__device__ __forceinline__ RawPtr raw_source(const RawSeg* segs, int R, size_t n, int c, int rec, bool& bad) {
+    const int k = (c >= 3) + (c >= 6) + (c >= 16) + (c >= 79) + (c >= 169) + (c >= 172) + (c >= 175);
+    const RawSeg s = segs[k];
+    bad = k == 2 && (rec < 0 || rec >= R);
+    const size_t row = k == 2 ? (size_t)(bad ? 0 : rec) : n;
+    return s.base + row * s.width + (c - s.col0);
+}
+
+constexpr int kRawBatch = 8;                   // loads a lane has in flight in the copy phase
+
+// One workgroup = two waves = 128 consecutive frames.  Phase 1: the lanes walk the workgroup's [frames, 178] block of the row-major
+// output in order (consecutive lanes on consecutive floats: whole-line stores, and loads that are consecutive within each source
+// array), eight elements per lane at a time, cast float64 -> float32 (round to nearest even, as torch.Tensor(ndarray)) and keep the
+// 79 columns the FK reads in LDS (row stride 79, odd: lane-per-row reads are conflict free).  Phase 2: one lane per frame runs the
+// chain of rohm_smplx_joints (the same device functions) on the cast values and adds the three leaf joints.
+__global__ __launch_bounds__(kRawFrames) void amass_preprocess_kernel(const RawArgs a) {
+    __shared__ float rows[kRawFrames * kParamCols];
+    __shared__ int recs[kRawFrames];
+    __shared__ RawSeg segs[8];
+    if (threadIdx.x == 0) raw_segments(a, segs);
+    const size_t n0 = (size_t)blockIdx.x * kRawFrames;
+    const int nf = (a.N - (long long)n0 < kRawFrames) ? (int)(a.N - (long long)n0) : kRawFrames;
+    if ((int)threadIdx.x < nf) recs[threadIdx.x] = a.rec_of_frame[n0 + threadIdx.x];
+    __syncthreads();
+    const int total = nf * kRawCols;
+    for (int base = threadIdx.x; base < total; base += kRawBatch * kRawFrames) {
+        double v[kRawBatch];
+        bool bad[kRawBatch];
+#pragma unroll
+        for (int u = 0; u < kRawBatch; ++u) {
+            const int idx = min(base + u * kRawFrames, total - 1);      // past the end: a valid address, the value is dropped
+            const int fl = idx / kRawCols;
+            v[u] = *raw_source(segs, a.R, n0 + fl, idx - fl * kRawCols, recs[fl], bad[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < kRawBatch; ++u) {
+            const int idx = base + u * kRawFrames;
+            if (idx < total) {
+                const int fl = idx / kRawCols, c = idx - fl * kRawCols;
+                const float x = bad[u] ? __builtin_nanf("") : (float)v[u];
+                a.params[n0 * kRawCols + idx] = x;
+                if (c < kParamCols) rows[fl * kParamCols + c] = x;
+            }
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x >= nf) return;
+    const float* w = rows + threadIdx.x * kParamCols;
+    const size_t n = n0 + threadIdx.x;
+    FkCtx f;
+    for (int j = 0; j < NJ; ++j) {
+        const int col = j == 0 ? 0 : 16 + (j - 1) * 3;
+        const float r[3] = {w[col], w[col + 1], w[col + 2]};
+        rodrigues(r, f.R[j]);
+    }
+    float beta[NBETA];
+    for (int k = 0; k < NBETA; ++k) beta[k] = w[6 + k];
+    rest_joints(a.Jt, a.Js, beta, f.Jr);
+    fk_forward(f, a.parents);
+    const float t[3] = {w[3], w[4], w[5]};
+    float* out = a.joints + n * kRawJoints * 3;
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[j * 3 + c] = f.P[j][c] + t[c];
+    // joints 22..24: P[j] = P[p] + G[p] (Jr[j] - Jr[p]); their own rotations turn nothing that is read
+    for (int j = NJ; j < kRawJoints; ++j) {
+        const int p = a.parents[j];
+        float off[3], wv[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float v = a.Jt[j * 3 + c];
+#pragma unroll
+            for (int k = 0; k < NBETA; ++k) v = fmaf(a.Js[(j * 3 + c) * NBETA + k], beta[k], v);
+            off[c] = v - f.Jr[p][c];
+        }
+        mat_vec(f.G[p], off, wv);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[j * 3 + c] = f.P[p][c] + wv[c] + t[c];
+    }
+}
+
 }  // namespace rohm
 
 using namespace rohm;
@@ -209,6 +325,30 @@ extern "C" int rohm_amass_batch(const float* repr_clean, const float* repr_noisy
     a.out_clean = out_clean; a.out_noisy = out_noisy; a.cond = cond; a.control = control_cond;
     prof::Scope ps("amass_batch", 0.0, 16.0 * (double)total, (hipStream_t)stream);
     hipLaunchKernelGGL(amass_batch_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    ROHM_LAUNCH_CHECK();
+    return ROHM_OK;
+}
+
+extern "C" int rohm_amass_preprocess(const rohm_smplx_t* h, const double* root_orient, const double* trans, const double* pose_body,
+                                     const double* pose_hand, const double* pose_jaw, const double* pose_eye, const double* betas,
+                                     const int32_t* rec_of_frame, int N, int R, float* joints, float* params, rohm_stream_t stream) {
+    ROHM_ARG_CHECK(h, "amass_preprocess: null handle");
+    ROHM_ARG_CHECK(h->J >= kRawJoints, "amass_preprocess: the body model has %d joints, joints 0..%d are needed", h->J, kRawJoints - 1);
+    for (int j = NJ; j < kRawJoints; ++j)
+        ROHM_ARG_CHECK(h->parents[j] >= 0 && h->parents[j] < NJ, "amass_preprocess: parents[%d] = %d is not one of the %d body joints", j,
+                       h->parents[j], NJ);
+    ROHM_ARG_CHECK(N >= 0 && R >= 0, "amass_preprocess: bad sizes (N=%d R=%d)", N, R);
+    if (N == 0) return ROHM_OK;
+    ROHM_ARG_CHECK(R >= 1, "amass_preprocess: %d frames but no recording", N);
+    ROHM_ARG_CHECK(root_orient && trans && pose_body && pose_hand && pose_jaw && pose_eye && betas && rec_of_frame && joints && params,
+                   "amass_preprocess: null argument");
+    RawArgs a;
+    a.root_orient = root_orient; a.trans = trans; a.pose_body = pose_body; a.pose_hand = pose_hand; a.pose_jaw = pose_jaw;
+    a.pose_eye = pose_eye; a.betas = betas; a.rec_of_frame = rec_of_frame; a.N = N; a.R = R;
+    a.Jt = h->d_Jt; a.Js = h->d_Js; a.parents = h->d_parents; a.joints = joints; a.params = params;
+    prof::Scope ps("amass_preprocess", 0.0, (8.0 * 168 + 4.0 * (kRawCols + kRawJoints * 3 + 1)) * (double)N, (hipStream_t)stream);
+    hipLaunchKernelGGL(amass_preprocess_kernel, dim3((unsigned)((N + kRawFrames - 1) / kRawFrames)), dim3(kRawFrames), 0,
+                       (hipStream_t)stream, a);
     ROHM_LAUNCH_CHECK();
     return ROHM_OK;
 }
