@@ -232,6 +232,12 @@ int rohm_output_process_f32(const float* h, const float* w, const float* b, floa
 int rohm_posenet_create(rohm_posenet_t** out, const rohm_posenet_weights* w, int d_model, int n_head,
                         int d_ff, int n_layer, int c_in, int c_out, int traj_dim, int device);
 void rohm_posenet_destroy(rohm_posenet_t* h);
+/* Bytes of caller-owned scratch one forward / sampling call on B clips of T frames needs (ROHM_ERR_WORKSPACE below it).  Besides the
+ * activations it holds, per sampling call, the loop-invariant cond half of the input embedding [B (T + 1), D] and -- for handles
+ * that fold layer 0's in-projection onto the packed input (d_model 512, d_ff 1024, 4 heads, <= 8 layers, T = 143; default on,
+ * ROHM_POSENET_INPROJ_FOLD=0 at create) -- that half pushed through the in-projection, [B (T + 1), 3 D]: 56.6 MB at B = 64.
+ * Such a handle itself holds, besides the weights, the folded weight [3 D, 320] and one in-projected timestep token per row of the
+ * positional table, [pe_len, 3 D]: 30.7 MB of device memory at pe_len = 5000. */
 size_t rohm_posenet_workspace_bytes(const rohm_posenet_t* h, int B, int T);
 /* 0: exact fp32 MFMA GEMMs (default); 3 / 2 / 16: the handle was created under ROHM_GEMM_PRECISION=bf16x6 / bf16x3 / fp16x3 and runs
  * the four Linears of every encoder layer (model/posenet.py:63-69) as split-bf16 GEMMs on planes. */

@@ -208,6 +208,11 @@ struct StackParams {
     // qkv = in_proj_0(h) -- model/posenet.py:85-92 up to the first encoder layer.
     const float* apack; int lda_pack; const float* w_embed; int ldw_embed; int k_embed;
     int S; const float* tab; const float* tab0; int ldtab, ldtab0, tab_by_row;
+    // w_fold != null (sampling loop with the cond half hoisted, tab_by_row): layer 0's in-projection skips h --
+    //   qkv0 = apack . w_fold^T + qtab[m]      w_fold = Win0 . Wx [3 D, ldw_fold] (k_embed columns used), qtab = tab . Win0^T + bin0 [M, 3 D]
+    // with the one row qtab0 [3 D] = (timestep token of this step) . Win0^T + bin0 for token 0 of every clip.  Token-0 rows of apack
+    // are zero.  The embed phase still writes h (layer 0's residual), but the meeting between the two leading phases goes away.
+    const float* w_fold; int ldw_fold; const float* qtab; const float* qtab0;
     // Diagnostics (null on every product path): when set, lane 0 of every workgroup stamps the 100 MHz wall clock (s_memrealtime) at the
     // seams of its phases into timeline[(block * kStackTimelineLayers + layer) * kStackTimelineStamps + k]
     // (rohm_posenet_set_stack_timeline; scripts/stack_timeline.py turns the stamps into per-phase spans and the in-stack attention rate).
@@ -235,7 +240,8 @@ struct StackParams {
 };
 // stamps of one layer: 0 layer entered, 1 qkv complete (attention starts), 2 attention done, 3 ctx complete (out-projection starts),
 // 4 out-projection + norm1 done, 5 y complete, 6 linear1 + GELU done, 7 ff complete, 8 linear2 + norm2 done, 9 h complete,
-// 10 next in-projection done (layer 7 with a tail: 9 h complete, 10 head + update + pack done); "layer" 8 = the leading phases: 0 entered, 1 embed done, 2 h complete, 3 in-projection of layer 0 done, 4 met
+// 10 next in-projection done (layer 7 with a tail: 9 h complete, 10 head + update + pack done); "layer" 8 = the leading phases: 0 entered, 1 embed done, 2 h complete
+// (folded in-projection: own h stores retired -- no meeting), 3 in-projection of layer 0 done, 4 met
 constexpr int kStackTimelineLayers = 9, kStackTimelineStamps = 12;
 int launch_encoder_stack(const StackParams& p, hipStream_t s);
 int encoder_chain_parts(int M, int D, int F);      // column tiles per clip (4 or 8), 0 = no chain form for this shape
@@ -265,10 +271,12 @@ __device__ __forceinline__ float wave_sum64(float v) {
 
 // erf-form GELU (activation="gelu", model/posenet.py:67; NOT the tanh approximation).  erf by Abramowitz-Stegun 7.1.26 (|abs err| <=
 // 1.5e-7, i.e. at fp32 resolution of the 1 + erf term) -- branch-free, one rcp + one exp, ~3x cheaper than the
-// library erff in a 72-element-per-lane epilogue.
+// library erff in a 72-element-per-lane epilogue.  The reciprocal is the hardware's v_rcp_f32 (1 ulp; its argument lies in [1, inf),
+// no denormals): __frcp_rn is a full IEEE division, eleven unpacked instructions per element, and a one-ulp change of t leaves the
+// formula's error against float64 erf-GELU where it was (4.7e-7 on [-8, 8]; tests/test_gpu_gelu_rcp.py).
 __device__ __forceinline__ float gelu_erf(float x) {
     const float z = fabsf(x) * 0.70710678118654752440f;
-    const float t = __frcp_rn(fmaf(0.3275911f, z, 1.0f));
+    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
     float p = fmaf(1.061405429f, t, -1.453152027f);
     p = fmaf(p, t, 1.421413741f);
     p = fmaf(p, t, -0.284496736f);

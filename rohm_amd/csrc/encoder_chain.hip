@@ -48,7 +48,8 @@ struct PhaseArgs {
     const float* R; int ldr;                       // RES_LN
     const float* gamma; const float* beta; float eps; int ln_dim;
     int qcols; float qscale;                       // QKV
-    int S; const float* tab; const float* tab0; int ldtab, ldtab0, tab_by_row;      // EMBED (common.h GemmParams)
+    int S; const float* tab; const float* tab0; int ldtab, ldtab0, tab_by_row;      // EMBED (common.h GemmParams); FOLD: tab = the per-row
+                                                                                    // table [M, ldtab], tab0 = the ONE row of every clip's token 0
     int m0, n0;
     float* row_stats; unsigned tag28; int tn, tiles_n;      // RES_LN: this row tile's slots, tag of this exchange
     unsigned* err; unsigned xcc1; int fault;
@@ -120,11 +121,17 @@ __device__ __forceinline__ void group_sync(unsigned long long* flags, int tn, in
 // HEAD (EPI_QKV, 384 columns, the stack at 4 parts per clip): the head-aligned tile (head_row; p.n0 = the head's first column), whose
 // epilogue hands q, k and v to the attention item through LDS instead of storing them: K into attention's K image, V into its V image
 // (both XOR-swizzled: attention_item's RESIDENT layout) and the Q fragments into *q_out.  The caller's next barrier publishes V.
-template <int BN, int EPI, bool PREF, bool SC1, bool REFETCH, bool HEAD = false, typename AfterLoop>
+// FOLD (EPI_QKV; layer 0's in-projection taken straight from the packed input, see encoder_stack_kernel): the tile starts from a table
+// row per output row instead of zero -- p.tab[m] for tokens >= 1, p.tab0 for token 0 of every clip (m0 is a clip's first row) -- and
+// adds no bias (the rows carry it).  The rows are loaded INTO the accumulators behind the prologue's wait: the 384-wide
+// tile has no registers for 54 more operands per lane.  hipcc waits for all of them (one vmcnt(0)) in front of the K loop, so the
+// load is exposed once per launch (~9 us at B = 64, NOTES 13.2); the loop body is untouched.  Token-0 rows of A must be zero (the pack keeps them so).
+template <int BN, int EPI, bool PREF, bool SC1, bool REFETCH, bool HEAD = false, bool FOLD = false, typename AfterLoop>
 __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, const int tid, AfterLoop&& after_loop,
                                            AtQFrags<2>* q_out = nullptr) {
     static_assert(EPI == EPI_BIAS_RES_LN || EPI == EPI_BIAS_GELU || EPI == EPI_QKV || EPI == EPI_EMBED, "chain phases: LN tail, GELU, QKV, embed");
     static_assert(!HEAD || (EPI == EPI_QKV && BN == 3 * AT_DH), "the head-aligned tile is one head's q | k | v");
+    static_assert(!FOLD || (EPI == EPI_QKV && PREF && !SC1), "the folded in-projection: prefetched weights, A from an earlier launch");
     constexpr int WN = BN / 4;
     // Every phase on v_mfma_f32_16x16x4_f32.  gemm_f32.hip's own launches run rows 0..127 of their 256- / 384-wide tiles on
     // v_mfma_f32_32x32x2_f32 (half the operand-register traffic per flop; measured faster there in round 2); INSIDE the stack the
@@ -215,7 +222,7 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
     const int nk = p.K / BK;                       // >= 16 here
     constexpr bool COL_LDS = BN >= 384;            // the 384-wide tile takes its bias row through LDS (gemm_f32.hip's choice for that width)
     if constexpr (!PREF) { dma_b(0, 0); dma_b(1, BK); }
-    if constexpr (COL_LDS) {
+    if constexpr (COL_LDS && !FOLD) {
         if (wave == 0) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -243,7 +250,7 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
     const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
     auto load_col = [&](int nb) __attribute__((always_inline)) {
         ColOps o{zero4, zero4, zero4};
-        if constexpr (EPI == EPI_EMBED) { /* the biases are part of the table rows */ }
+        if constexpr (EPI == EPI_EMBED || FOLD) { /* the biases are part of the table rows */ }
         else if constexpr (COL_LDS) o.bias = *reinterpret_cast<const f32x4*>(colrow + (nb - n0));
         else o.bias = *reinterpret_cast<const f32x4*>(p.bias + nb);
         if constexpr (RES) {
@@ -282,6 +289,19 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
     // chunks, the bias row, A chunk 0 -- retires first: loads return in order, and no store of this wave is in flight here)
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(A_ITERS) : "memory");
     __syncthreads();
+    if constexpr (FOLD) {
+        // behind the wait (the asm above pins them there: the counted wait must see DMAs only).  The generated code drains them
+        // with one vmcnt(0) ahead of the first MFMA: exposed, not hidden under chunk 0
+#pragma unroll
+        for (int r = 0; r < NRB; ++r) {
+            const float* const row = (r == 0 && li == 0) ? p.tab0 : p.tab + (size_t)(m0 + r * 16 + li) * p.ldtab;
+#pragma unroll
+            for (int c = 0; c < NCB; ++c) {
+                const int t = wave * WN + c * 16 + lg * 4;
+                acc16[r * NCB + c] = *reinterpret_cast<const f32x4*>(row + (HEAD ? head_row(n0, t) : n0 + t));
+            }
+        }
+    }
     read_frags(f0, 0, 0);
     constexpr int NG = READS;
     constexpr int MF = (MFMAS + NG - 1) / NG;
@@ -473,7 +493,7 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
                 const f32x4 a = acc16[r * NCB + c];
                 f32x4 v;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = a[q] + col[c].bias[q];
+                for (int q = 0; q < 4; ++q) v[q] = FOLD ? a[q] : a[q] + col[c].bias[q];
                 if (c < 2) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) v[q] *= p.qscale;
@@ -506,7 +526,7 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
         for_units([&](int, int cg, int m, int nb, f32x4 a) __attribute__((always_inline)) {
             f32x4 v;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = a[q] + col[cg].bias[q];
+            for (int q = 0; q < 4; ++q) v[q] = FOLD ? a[q] : a[q] + col[cg].bias[q];
             if constexpr (EPI == EPI_BIAS_GELU) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = gelu_erf(v[q]);
@@ -842,13 +862,28 @@ __global__ __launch_bounds__(256) void encoder_stack_kernel(StackParams p) {
     a.A = p.apack; a.lda = p.lda_pack; a.W = p.w_embed; a.ldw = p.ldw_embed; a.C = p.h; a.ldc = p.D; a.K = p.k_embed; a.n0 = tn * BNL;
     a.S = p.S; a.tab = p.tab; a.tab0 = p.tab0; a.ldtab = p.ldtab; a.ldtab0 = p.ldtab0; a.tab_by_row = p.tab_by_row;
     stamp(8, 0);
-    gemm_phase<BNL, EPI_EMBED, false, false, G == 8>(a, smem, tid, [&]() { prefetch_w<BNQ, HEAD>(p.layer[0].in_w, p.D, n0q(), smem, tid, wave_u); });
+    // fold (uniform over the launch; the sampling loop): layer 0's in-projection contracts the packed x_t with w_fold = Win0 . Wx over
+    // K = k_embed and starts from the rows of qtab = econd . Win0^T + bin0 -- qkv0 without h.  h is still written (norm1 of layer 0
+    // adds it as the residual: each workgroup re-reads its OWN columns), but nobody else reads it, so the meeting goes away
+    const bool fold = p.w_fold != nullptr;
+    gemm_phase<BNL, EPI_EMBED, false, false, G == 8>(a, smem, tid, [&]() {
+        prefetch_w<BNQ, HEAD>(fold ? p.w_fold : p.layer[0].in_w, fold ? p.ldw_fold : p.D, n0q(), smem, tid, wave_u);
+    });
     stamp(8, 1);
-    group_sync(fl, tn, G, ep, xcc1, p.xln_err, tid);
-    stamp(8, 2);
-    a.A = p.h; a.lda = p.D; a.W = p.layer[0].in_w; a.ldw = p.D; a.C = p.qkv; a.ldc = 3 * p.D; a.K = p.D; a.bias = p.layer[0].in_b;
-    a.n0 = n0q();
-    gemm_phase<BNQ, EPI_QKV, true, true, G == 8, HEAD>(a, smem, tid, []() {}, &qh);
+    a.C = p.qkv; a.ldc = 3 * p.D; a.n0 = n0q();
+    if (fold) {
+        // the counted wait of the next prologue assumes that no store of this wave is in flight (stores and loads retire in no
+        // common order): the h tile's stores -- what the meeting's vmcnt(0) covers on the other path
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        stamp(8, 2);
+        a.W = p.w_fold; a.ldw = p.ldw_fold; a.tab = p.qtab; a.ldtab = 3 * p.D; a.tab0 = p.qtab0;      // A, lda, K: the embed's
+        gemm_phase<BNQ, EPI_QKV, true, false, G == 8, HEAD, true>(a, smem, tid, []() {}, &qh);
+    } else {
+        group_sync(fl, tn, G, ep, xcc1, p.xln_err, tid);
+        stamp(8, 2);
+        a.A = p.h; a.lda = p.D; a.W = p.layer[0].in_w; a.ldw = p.D; a.K = p.D; a.bias = p.layer[0].in_b;
+        gemm_phase<BNQ, EPI_QKV, true, true, G == 8, HEAD>(a, smem, tid, []() {}, &qh);
+    }
     stamp(8, 3);
     if constexpr (HEAD) __syncthreads();      // this workgroup's K and V images are complete: its attention item needs nothing else
     else group_sync(fl + 8, tn, G, ep, xcc1, p.xln_err, tid);
@@ -921,6 +956,8 @@ int launch_encoder_stack(const StackParams& p, hipStream_t s) {
     StackParams q = p;
     q.tiles_m = p.M / chain::BM;
     const int groups8 = (q.tiles_m + kNumXCD - 1) / kNumXCD * kNumXCD;
+    ROHM_ARG_CHECK(!p.w_fold || (p.qtab && p.qtab0 && p.ldw_fold % 4 == 0 && p.ldw_fold >= p.k_embed && p.tab_by_row),
+                   "encoder_stack: bad operands of the folded in-projection");
     ROHM_ARG_CHECK(!p.tail || (p.D == 512 && p.t_out_w && p.t_out_b && p.t_x && p.t_cond && p.t_C - p.t_traj == 272 &&
                                p.t_T == chain::BM - 1 && p.t_traj > 0 && (!p.t_apack || p.t_lda >= p.t_C)),
                    "encoder_stack: the closing head / update / pack phase needs whole 144-token clips, d_model 512 and 272 predicted channels");

@@ -48,6 +48,11 @@ struct rohm_posenet {
     int KX;            // padded K of the x_t half alone
     float* w_embed_x;  // [D, KX]   = [Wx | 0]: the per-step embed of the sampling loop, whose cond half is computed once per call
     bool cond_hoist;   // (default on; ROHM_POSENET_COND_HOIST=0: the full [x_t | cond] contraction every step)
+    // Layer 0's in-projection folded onto the packed input (stack form of the sampling loop; default on, ROHM_POSENET_INPROJ_FOLD=0):
+    // nothing nonlinear lies between h0 = x_t . Wx^T + econd and qkv0 = h0 . Win0^T + bin0, so qkv0 = x_t . w_fold^T + (econd . Win0^T + bin0).
+    // The switch is w_fold itself: null when it is off or the shape has no stack form.
+    float* w_fold;     // [3 D, KX]  = [Win0 . Wx | 0], accumulated in double, rounded once (null: no fold on this handle)
+    float* tokq;       // [pe_len, 3 D]  tok_table . Win0^T + bin0: the token-0 row of qkv0 for every t
     float* tab;        // [kMaxTok, D]  pe[tok] + bx + bc
     float* pe;         // [pe_len, D]
     int pe_len;
@@ -240,6 +245,19 @@ __global__ void build_embed_kernel(const float* __restrict__ wx, const float* __
     }
 }
 
+// w_fold[n][k] = sum_j Win0[n][j] Wx[j][k] for k < C, 0 in the pad columns (double accumulation, one rounding).
+__global__ __launch_bounds__(256) void build_fold_kernel(const float* __restrict__ win, const float* __restrict__ wx, float* __restrict__ w_fold,
+                                                         int N, int D, int C, int KX) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < N * KX) {
+        const int n = i / KX, k = i % KX;
+        double acc = 0.0;
+        if (k < C)
+            for (int j = 0; j < D; ++j) acc += (double)win[(size_t)n * D + j] * (double)wx[(size_t)j * C + k];
+        w_fold[i] = (float)acc;
+    }
+}
+
 __global__ void build_tab_kernel(const float* __restrict__ pe, const float* __restrict__ bx,
                                  const float* __restrict__ bc, float* __restrict__ tab, int rows, int D) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -281,6 +299,7 @@ struct Workspace {
     float* sk;                    // scratch of the stream-K output head (common.h gemm_sk_*): flags, partial tiles
     float* econd;                 // [M, D] cond half of the input embedding + positional table + biases (sampling loop)
     float* chain_flags;           // "my tile is stored" flags of the encoder chain (common.h ChainParams::flags)
+    float* econdq;                // [M, 3 D] econd . Win0^T + bin0 (sampling loop, folded in-projection of layer 0); null without the fold
     int64_t* t_all;
     size_t floats;
 };
@@ -320,6 +339,10 @@ static Workspace carve(const rohm_posenet* p, int B, int T, float* base) {
     w.sk = take(gemm_sk_scratch_bytes() / sizeof(float));
     w.econd = take(M * p->D);
     w.chain_flags = take(encoder_chain_flag_bytes((int)M) / sizeof(float));
+    // last, so that every other region stays where it was; only shapes that can run the stack pay for it (a static property of the
+    // handle and the shape: the size must not move with the exchange fallback)
+    const bool foldable = p->w_fold && T + 1 == 144 && encoder_chain_parts((int)M, p->D, p->F) != 0;
+    w.econdq = foldable ? take(M * 3 * p->D) : nullptr;
     w.floats = off;
     return w;
 }
@@ -387,10 +410,11 @@ static EncoderPlan plan_encoder(const rohm_posenet* p, int B, int S) {
 // `*tail_ran` says whether it did (x0_out is then NOT written: tail->x0 is).
 static int run_network(const rohm_posenet* p, const Workspace& w, const int64_t* t_dev, int64_t t_host,
                        const float* tok_pre, float* x0_out, int B, int T, hipStream_t s, bool cond_done = false,
-                       const TailArgs* tail = nullptr, bool* tail_ran = nullptr) {
+                       const TailArgs* tail = nullptr, bool* tail_ran = nullptr, bool fold = false) {
     if (tail_ran) *tail_ran = false;
     const int S = T + 1, D = p->D, M = B * S;
     // timestep token(s): per sample from device timesteps, or one precomputed row shared by the batch
+    const float* tokq_row = nullptr;      // fold: the token-0 row of qkv0 for this step's t (one row for the batch, like tok_pre)
     if (!tok_pre) {
         if (t_dev) {
             prof::Scope ps("gather_tokens", 0.0, 8.0 * D * B, s);
@@ -399,6 +423,7 @@ static int run_network(const rohm_posenet* p, const Workspace& w, const int64_t*
         } else {
             int64_t t = t_host < 0 ? 0 : (t_host >= p->pe_len ? p->pe_len - 1 : t_host);
             tok_pre = p->tok_table + (size_t)t * D;
+            if (p->tokq) tokq_row = p->tokq + (size_t)t * 3 * D;
         }
     }
     int rc;
@@ -467,6 +492,9 @@ static int run_network(const rohm_posenet* p, const Workspace& w, const int64_t*
         StackParams c{};
         c.apack = ge.A; c.lda_pack = ge.lda; c.w_embed = ge.W; c.ldw_embed = ge.ldw; c.k_embed = ge.K;
         c.S = S; c.tab = ge.tab; c.tab0 = ge.tab0; c.ldtab = ge.ldtab; c.ldtab0 = ge.ldtab0; c.tab_by_row = ge.tab_by_row;
+        if (fold && cond_done && tokq_row && w.econdq) {
+            c.w_fold = p->w_fold; c.ldw_fold = p->KX; c.qtab = w.econdq; c.qtab0 = tokq_row;
+        }
         c.h = h; c.y = y; c.ff = w.ff; c.qkv = w.qkv; c.ctx = w.ctx;
         c.M = M; c.D = D; c.F = p->F; c.L = p->L; c.n_head = p->H; c.qscale = qscale_of(p); c.ln_eps = 1e-5f;
         for (int l = 0; l < p->L; ++l) {
@@ -620,6 +648,8 @@ static int launch_finish_pack(const rohm_posenet* p, float* x0, const float* con
 //   ROHM_POSENET_CHAIN_ANY=1     chain / stack at every batch size that has the form (tests)
 //   ROHM_POSENET_STACK_TAIL=0    head, DDPM update and the next step's pack as their own launches behind the stack
 //   ROHM_POSENET_COND_HOIST=0    the full [x_t | cond] embedding every step instead of the cond half once per sampling call
+//   ROHM_POSENET_INPROJ_FOLD=0   sampling loop, stack form: layer 0's in-projection from h instead of straight from the packed x_t
+//                                (read in rohm_posenet_create, where it sizes the arena: off = no w_fold / tokq)
 //   ROHM_GEMM_PRECISION=fp32|bf16x6|bf16x3|fp16x3 (default fp32): the precision ladder, split GEMMs on planes
 //   ROHM_PP_LNFOLD=0             plane modes: LayerNorm as its own kernel instead of folded into the plane GEMMs
 static int read_knobs(rohm_posenet* p) {
@@ -678,6 +708,10 @@ int rohm_posenet_create(rohm_posenet_t** out, const rohm_posenet_weights* w, int
     const size_t o_embed = cnt(D * p->KP), o_tab = cnt((size_t)kMaxTok * D), o_pe = cnt((size_t)w->pe_len * D);
     const size_t o_embed_x = cnt(D * p->KX);
     const size_t o_tok = cnt((size_t)w->pe_len * D);
+    // the fold's operands exist where the stack form does (plan_encoder: 4 heads of 128, <= 8 layers, 272 predicted channels aside)
+    const char* fold_env = getenv("ROHM_POSENET_INPROJ_FOLD");      // read here, not in read_knobs: the arena is sized by it
+    const bool can_fold = !(fold_env && fold_env[0] == '0') && d_model == 512 && d_ff == 1024 && n_head == 4 && n_layer <= 8;
+    const size_t o_fold = cnt(can_fold ? 3 * D * p->KX : 0), o_tokq = cnt(can_fold ? (size_t)w->pe_len * 3 * D : 0);
     const size_t o_w0 = cnt(D * D), o_b0 = cnt(D), o_w2 = cnt(D * D), o_b2 = cnt(D);
     const size_t o_ow = cnt((size_t)c_out * D), o_ob = cnt(c_out);
     const size_t o_tmp = cnt(D * D);                      // staging for transposes / embed build
@@ -709,6 +743,7 @@ int rohm_posenet_create(rohm_posenet_t** out, const rohm_posenet_weights* w, int
     p->w_embed = a + o_embed; p->w_embed_x = a + o_embed_x; p->tab = a + o_tab; p->pe = a + o_pe; p->tok_table = a + o_tok;
     p->t_w0T = a + o_w0; p->t_b0 = a + o_b0; p->t_w2T = a + o_w2; p->t_b2 = a + o_b2;
     p->out_w = a + o_ow; p->out_b = a + o_ob;
+    p->w_fold = can_fold ? a + o_fold : nullptr; p->tokq = can_fold ? a + o_tokq : nullptr;
     if (int rc = read_knobs(p)) {
         (void)hipFree(p->arena);
         delete p;
@@ -785,6 +820,27 @@ int rohm_posenet_create(rohm_posenet_t** out, const rohm_posenet_weights* w, int
     }
 #undef PUT
     ROHM_HIP_CHECK(hipDeviceSynchronize());
+    if (p->w_fold) {      // wx is still in tmp2; layer 0's in-projection has just arrived
+        const LayerW& l0 = p->layers[0];
+        hipLaunchKernelGGL(build_fold_kernel, dim3((unsigned)((3 * D * p->KX + th - 1) / th)), dim3(th), 0, 0, l0.in_w, wx, p->w_fold,
+                           (int)(3 * D), (int)D, c_in, p->KX);
+        const hipError_t ef = hipGetLastError();
+        if (ef != hipSuccess) {
+            set_error("posenet_create: launch of build_fold_kernel failed: %s", hipGetErrorString(ef));
+            (void)hipFree(p->arena);
+            delete p;
+            return ROHM_ERR_HIP;
+        }
+        GemmParams g{};
+        g.A = p->tok_table; g.lda = (int)D; g.W = l0.in_w; g.ldw = (int)D; g.C = p->tokq; g.ldc = (int)(3 * D);
+        g.M = p->pe_len; g.N = (int)(3 * D); g.K = (int)D; g.bias = l0.in_b;
+        if (launch_gemm(g, EPI_BIAS, 0) != ROHM_OK || hipDeviceSynchronize() != hipSuccess) {
+            set_error("posenet_create: building the folded in-projection failed");
+            (void)hipFree(p->arena);
+            delete p;
+            return ROHM_ERR_HIP;
+        }
+    }
     for (auto& d : p->layers) {
         d.in_wp = d.out_wp = d.l1_wp = d.l2_wp = d.l1_wpf = d.in_wpf = nullptr;
         d.l1_cf = d.l1_df = d.in_cf = d.in_df = nullptr;
@@ -995,6 +1051,16 @@ int rohm_posenet_sample_loop(const rohm_posenet_t* h, float* x, const float* con
         g.M = B * S; g.N = h->D; g.K = h->KP; g.S = S; g.tab = h->tab; g.tab0 = h->tok_table; g.ldtab = h->D; g.ldtab0 = 0;
         if ((rc = launch_gemm(g, EPI_EMBED, s))) return rc;
     }
+    // ... and, where the steps run as stack launches, layer 0's in-projection of that half: econdq = econd . Win0^T + bin0 (its token-0
+    // rows are never read: the steps take tokq's row of their t there).  ONE more launch per call; the steps then contract x_t with
+    // w_fold over K = KX instead of h with Win0 over K = D, and drop the meeting in front of it.
+    const bool fold = hoist && w.econdq && plan_encoder(h, B, T + 1).stacked;
+    if (fold) {
+        GemmParams g{};
+        g.A = w.econd; g.lda = h->D; g.W = h->layers[0].in_w; g.ldw = h->D; g.C = w.econdq; g.ldc = 3 * h->D;
+        g.M = B * (T + 1); g.N = 3 * h->D; g.K = h->D; g.bias = h->layers[0].in_b;
+        if ((rc = launch_gemm(g, EPI_BIAS, s))) return rc;
+    }
     // timestep tokens come from the table built at create (the embedder depends on t only, heads.py:145-146)
     for (int i = 0; i < n_steps; ++i) {
         prof::set_step(i);
@@ -1011,7 +1077,7 @@ int rohm_posenet_sample_loop(const rohm_posenet_t* h, float* x, const float* con
         TailArgs tail{x, cond, nz, (x0_last && i == n_steps - 1) ? x0_last : nullptr, (i + 1 < n_steps) ? w.apack : nullptr,
                       c1, c2, sigma, pass_counter(w), i};
         bool tail_ran = false;
-        if ((rc = run_network(h, w, nullptr, t_model[i], nullptr, x0, B, T, s, hoist, &tail, &tail_ran))) return rc;
+        if ((rc = run_network(h, w, nullptr, t_model[i], nullptr, x0, B, T, s, hoist, &tail, &tail_ran, fold))) return rc;
         if (tail_ran) continue;
         if (i + 1 < n_steps) {
             if ((rc = launch_finish_pack(h, x0, cond, x, nz, w.apack, c1, c2, sigma, B, T, pass_counter(w), s))) return rc;

@@ -30,9 +30,11 @@ def _flops_per_layer(B, D=512, F=1024, S=144, H=4):
             'linear2_norm2': 2.0 * M * F * D, 'in_proj_next': 2.0 * M * 3 * D * D}
 
 
-def measure(net, B, T=143, reps=5, device='cuda:0', seed=0):
+def measure(net, B, T=143, reps=5, device='cuda:0', seed=0, steps_per_call=2):
     """Stamp `reps` one-step launches of the fused sampling loop (the shipped path: the stack with its leading embed / in-projection
-    phases) at batch size B and return the per-phase record.  Needs a handle that runs the stack (exchange_mode bit 5) at this B."""
+    phases) at batch size B and return the per-phase record.  Needs a handle that runs the stack (exchange_mode bit 5) at this B.
+    `steps_per_call` >= 4 stamps the launches of a long sampling call: the cond half of the embedding hoisted (embed with K = 320) and
+    layer 0's in-projection folded onto the packed input (no wait_embed); the default 2 stamps a short call's full leading phases."""
     dev = torch.device(device)
     nat = net.native(dev)
     if not nat.exchange_mode & 32 or B < 32:
@@ -44,20 +46,21 @@ def measure(net, B, T=143, reps=5, device='cuda:0', seed=0):
     g = torch.Generator(device=dev).manual_seed(seed)
     x = torch.randn(B, 294, 1, T, device=dev, generator=g)
     cond = torch.randn(B, 294, 1, T, device=dev, generator=g)
-    noise = torch.randn(2, B, 294, 1, T, device=dev, generator=g)
-    coef = np.asarray([[0.02, 0.98, 0.05]] * 2, np.float32)
-    net.sample_loop_native(x, cond, [500, 499], coef, noise)          # warm: weights in L2 / MALL, clocks up
+    n = int(steps_per_call)
+    noise = torch.randn(n, B, 294, 1, T, device=dev, generator=g)
+    coef = np.asarray([[0.02, 0.98, 0.05]] * n, np.float32)
+    net.sample_loop_native(x, cond, [500 - k for k in range(n)], coef, noise)          # warm: weights in L2 / MALL, clocks up
     check(lib().rohm_posenet_set_stack_timeline(nat.handle, ptr(buf), nbytes, B), 'rohm_posenet_set_stack_timeline')
     recs, wall = [], []
     try:
         for r in range(reps):
-            # two steps per call; the second launch's stamps are the ones left in the buffer (steady state: operands warm)
+            # n steps per call; the last launch's stamps are the ones left in the buffer (steady state: operands warm)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            net.sample_loop_native(x, cond, [498 - 2 * r, 497 - 2 * r], coef, noise)
+            net.sample_loop_native(x, cond, [498 - n * r - k for k in range(n)], coef, noise)
             e1.record()
             torch.cuda.synchronize(dev)
-            wall.append(e0.elapsed_time(e1) * 1e3 / 2)
+            wall.append(e0.elapsed_time(e1) * 1e3 / n)
             recs.append(buf.cpu().numpy().reshape(-1, LAYERS, STAMPS)[:groups8 * G].astype(np.float64) * TICK_US)      # sized for 8 parts per clip
     finally:
         check(lib().rohm_posenet_set_stack_timeline(nat.handle, None, 0, 0), 'rohm_posenet_set_stack_timeline')
