@@ -897,6 +897,27 @@ int rohm_traj_report(const float* joints_clean, const float* joints_noisy, const
                      long long rot_clean_stride, const float* rot_rec, long long rot_rec_stride, int B, int T,
                      double* out, float* elems, rohm_stream_t stream);
 
+/* Export of a reconstruction (csrc/export.hip): rows of the 294-channel representation -> per-frame SMPL-X parameters in
+ * scene or camera coordinates, one launch for all N frames of a recording.  The inverse of rohm_smplx_frames_to_world +
+ * rohm_clips_build; what eval_prox_egobody.py:275-310 does per clip on the host (recover_from_repr_smpl 'smplx_params',
+ * inv(trans_scene2cano)), applied to the parameters as update_globalRT_for_smplx with delta_T given
+ * (utils/other_utils.py:221-240).
+ * repr is addressed as in rohm_repr_joints: element (c, t, ch) at repr[c*in_stride_b + t*in_stride_t + ch*in_stride_c],
+ * c < C, t < T, ch < 294; mean294 / std294 (both or neither) de-normalise in float32 as x * std + mean, two rounded
+ * operations.  transf [C,4,4] float32 (scene -> canonical; NULL = identity) is inverted in float64 as a general affine map;
+ * rigid [4,4] float64 (NULL = identity) is applied after that inverse: A = rigid . inv(transf[c]).  Output frame n is
+ * taken from clip frame_clip[n], row frame_t[n] (device int32 [N]); an index outside [0, C) x [0, T) yields a NaN row,
+ * never a read outside the arrays.  Per frame, float64 after the de-normalisation: R = Gram-Schmidt of smplx_rot_6d
+ * (quaternion.py:482-501) and of the 21 body joints; d = rest-pose pelvis of the frame's betas (folded regressor of h);
+ * R' = A_R R, t' = A_R (t + d) + A_t - d; rotation vectors through the quaternion with an atan2 angle (|aa| <= pi).
+ * params [N,79] float64 = global_orient 3, transl 3, betas 10, body_pose 63 (the smplx_world layout rohm_clips_build
+ * reads); contact [N,4] float32 (may be NULL) = the foot-contact channels.  No atomics: the same input gives the same
+ * bits.  N == 0 returns without a launch. */
+int rohm_export_smplx(const rohm_smplx_t* h, const float* repr, long long in_stride_b, long long in_stride_t,
+                      long long in_stride_c, const float* mean294, const float* std294, const float* transf,
+                      const double* rigid, const int* frame_clip, const int* frame_t, int C, int T, int N,
+                      double* params, float* contact, rohm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -231,6 +231,8 @@ SIGNATURES = {
     'rohm_result_rows': (C.c_int, [C.POINTER(ResultRowsItem), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'rohm_traj_report': (C.c_int, [C.c_void_p] * 6 + [C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p,
                                                        C.c_void_p, C.c_void_p]),
+    'rohm_export_smplx': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong] + [C.c_void_p] * 6 +
+                          [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

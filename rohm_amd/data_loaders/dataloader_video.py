@@ -84,6 +84,29 @@ def read_stats(logdir):
     return mean_dict, std_dict, mean, std
 
 
+def read_cam2world(dataset, base_dir, recording_name, info=None, return_master=False):
+    """The camera -> world transform [4, 4] the loaders apply to a recording's fits: PROX's cam2world/<scene>.json
+    (dataloader_video.py:100), EgoBody's calibration chain kinect12_to_world . kinect_<sub>to12_color for a sub view
+    (:238-250).  `info`: EgoBody's `read_egobody_info` row when the caller has it already; `return_master` also returns
+    EgoBody's master -> world transform."""
+    if dataset == 'prox':
+        scene_name = recording_name.split('_')[0]
+        return np.array(read_json(os.path.join(base_dir, 'cam2world', scene_name + '.json')))
+    if dataset != 'egobody':
+        raise ValueError(f'dataset {dataset!r} not defined')
+    if info is None:
+        info = read_egobody_info(base_dir, recording_name)
+    view = info['view']
+    cal = os.path.join(base_dir, 'calibrations', recording_name, 'cal_trans')
+    master2world = np.asarray(read_json(os.path.join(cal, 'kinect12_to_world', info['scene_name'] + '.json'))['trans'])
+    if view != 'master':
+        sub2main = np.asarray(read_json(os.path.join(cal, f'kinect_{EGOBODY_SUB_KINECT[view]}to12_color.json'))['trans'])
+        cam2world = np.matmul(master2world, sub2main)
+    else:
+        cam2world = master2world
+    return (cam2world, master2world) if return_master else cam2world
+
+
 def read_prox_recording(init_root, base_dir, recording_name, joints_num=22):
     """dataloader_video.py:95-158: everything `read_data_prox` takes from the disk."""
     fitting_dir = os.path.join(init_root, recording_name, 'results')
@@ -92,7 +115,7 @@ def read_prox_recording(init_root, base_dir, recording_name, joints_num=22):
     kp_dir = os.path.join(base_dir, 'keypoints_openpose', recording_name)
     return {
         'scene_name': scene_name, 'frame_names': frame_names, 'params': read_fittings(fitting_dir, frame_names),
-        'cam2world': np.array(read_json(os.path.join(base_dir, 'cam2world', scene_name + '.json'))),
+        'cam2world': read_cam2world('prox', base_dir, recording_name),
         'color_cam': read_json(os.path.join(base_dir, 'calibration', 'Color.json')),
         'keypoints': np.asarray([read_keypoints(os.path.join(kp_dir, n + '_keypoints.json'), joints_num) for n in frame_names]),
         'mask_joint': np.load(os.path.join(base_dir, 'mask_joint', recording_name, 'mask_joint.npy')),
@@ -128,13 +151,7 @@ def read_egobody_recording(init_root, base_dir, recording_name, joints_num=22):
     view, idx = info['view'], info['body_idx']
     fitting_dir = os.path.join(init_root, recording_name, f'body_idx_{idx}', 'results')
     frame_names = sorted(os.listdir(fitting_dir))
-    cal = os.path.join(base_dir, 'calibrations', recording_name, 'cal_trans')
-    master2world = np.asarray(read_json(os.path.join(cal, 'kinect12_to_world', info['scene_name'] + '.json'))['trans'])
-    if view != 'master':
-        sub2main = np.asarray(read_json(os.path.join(cal, f'kinect_{EGOBODY_SUB_KINECT[view]}to12_color.json'))['trans'])
-        cam2world = np.matmul(master2world, sub2main)
-    else:
-        cam2world = master2world
+    cam2world, master2world = read_cam2world('egobody', base_dir, recording_name, info, return_master=True)
     kp_dir = os.path.join(base_dir, 'keypoints_cleaned', recording_name, view)
     info.update({
         'frame_names': frame_names, 'params': read_fittings(fitting_dir, frame_names),

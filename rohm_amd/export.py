@@ -1,0 +1,394 @@
+"""Export a reconstruction as per-frame SMPL-X parameters and meshes in scene or camera coordinates.
+
+The drivers leave the reference's result pickle: per clip a de-normalised 294-channel representation in the clip's own
+canonical frame plus `trans_scene2cano_list`.  This module goes the other way round from the loaders
+(`frames.frames_to_world` -> `clips.build_clips`): representation rows -> axis-angle SMPL-X parameters in the scene's or
+the camera's frame, one track per recording, in one launch (`rohm_export_smplx`, csrc/export.hip); vertices come from the
+existing skinning (`rohm_smplx_forward`) fed with the exported parameters, so they are in the chosen frame already.
+
+    python -m rohm_amd.export --dataset prox --saved_data_dir test_results/results_prox/test_prox_... \\
+        --recordings N0Sofa_00034_01 --dataset_root /data/PROX --body_model_path body_models/smplx_model \\
+        --out exported --frame camera --formats npz,prox_fits --meshes ply --mesh_interval 30 --clip_len 145
+
+Stitching: clip c holds recording frames c * (clip_len - overlap_len) ... + T - 1 (T rows per clip); a frame two clips share
+is taken from the earlier clip (`keep='first'`) or the later one (`keep='last'`); nothing is blended.  `betas='mean'`
+replaces every frame's shape by the recording's mean shape before the kernel runs (so the pelvis offset and the translation
+are consistent with it) -- a departure from the reference, which keeps per-frame shapes.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import pickle
+import sys
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from .body_model import lbs_forward, native_for
+from ._lib import check, lib, ptr, stream_ptr
+
+PARAM_COLS = {'global_orient': (0, 3), 'transl': (3, 6), 'betas': (6, 16), 'body_pose': (16, 79)}      # the smplx_world layout
+FORMATS = ('npz', 'prox_fits')
+
+
+# ---- stitching -----------------------------------------------------------------------------------------------------------
+def plan_frames(n_clips, T, clip_len, overlap_len, keep='first'):
+    """Which (clip, row) every recording frame is exported from -> (frame_clip int32 [n], frame_t int32 [n], n_frames).
+
+    Clip c holds recording frames c * (clip_len - overlap_len) ... + T - 1.  A frame two clips share goes to the earlier clip
+    with keep='first' and to the later one with keep='last'.  Frames after the last clip's last row are not part of the
+    export: n_frames = (n_clips - 1) * (clip_len - overlap_len) + T."""
+    if keep not in ('first', 'last'):
+        raise ValueError(f"keep must be 'first' or 'last', got {keep!r}")
+    n_clips, T, stride = int(n_clips), int(T), int(clip_len) - int(overlap_len)
+    if n_clips < 0 or T < 1 or stride < 1:
+        raise ValueError(f'need n_clips >= 0, T >= 1 and clip_len > overlap_len (got {n_clips}, {T}, {clip_len}, {overlap_len})')
+    if n_clips > 1 and T < stride:
+        raise ValueError(f'clips of {T} rows every {stride} frames leave frames uncovered')
+    if n_clips == 0:
+        return np.zeros(0, np.int32), np.zeros(0, np.int32), 0
+    n_frames = (n_clips - 1) * stride + T
+    f = np.arange(n_frames, dtype=np.int64)
+    last = np.minimum(f // stride, n_clips - 1)
+    first = np.maximum(-((-(f - T + 1)) // stride), 0)          # ceil((f - T + 1) / stride)
+    clip = first if keep == 'first' else last
+    return clip.astype(np.int32), (f - clip * stride).astype(np.int32), n_frames
+
+
+def first_pass_rows(trans_scene2cano):
+    """Rows of a drivers' pickle that belong to the first pass over the recording.  The drivers' batch loop restarts its
+    loader when it runs out (`drivers.results.step_schedule`): a clip count that is a multiple of the batch size gets its first
+    batch a second time.  The first row r >= 1 whose trans_scene2cano equals row 0's bit for bit starts that repeat."""
+    a = np.ascontiguousarray(np.asarray(trans_scene2cano))
+    for r in range(1, len(a)):
+        if a[r].tobytes() == a[0].tobytes():
+            return r
+    return len(a)
+
+
+# ---- the export ----------------------------------------------------------------------------------------------------------
+class ExportResult:
+    """Device tensors of an exported track: params79 [N, 79] float64 (global_orient 3, transl 3, betas 10, body_pose 63) and its
+    four views, joints [N, 22, 3] float32, contact [N, 4] float32, frame_clip / frame_t int32 [N], coordinate_frame."""
+
+    def __init__(self, params79, joints, contact, frame_clip, frame_t, coordinate_frame):
+        self.params79, self.joints, self.contact = params79, joints, contact
+        self.frame_clip, self.frame_t, self.coordinate_frame = frame_clip, frame_t, coordinate_frame
+        for k, (a, b) in PARAM_COLS.items():
+            setattr(self, k, params79[:, a:b])
+
+    def __len__(self):
+        return int(self.params79.shape[0])
+
+    def pose_f32(self):
+        """[N, 22, 3] float32 axis-angle, global orient first (what rohm_smplx_joints / rohm_smplx_forward take)."""
+        return torch.cat([self.global_orient, self.body_pose], dim=1).float().reshape(-1, 22, 3).contiguous()
+
+
+def _device_f32(x, device):
+    if torch.is_tensor(x):
+        return x.detach().to(device=device, dtype=torch.float32)
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32)).to(device)
+
+
+def _layout(x):
+    if x.dim() == 3 and x.shape[2] == 294:
+        return 'btc', x.shape[0], x.shape[1]
+    if x.dim() == 4 and x.shape[1] == 294 and x.shape[2] == 1:
+        return 'bc1t', x.shape[0], x.shape[3]
+    raise ValueError(f'expected [C, T, 294] or [C, 294, 1, T], got {tuple(x.shape)}')
+
+
+def _joints(nat, pose, betas, transl):
+    N = pose.shape[0]
+    out = torch.empty(N, 22, 3, device=pose.device, dtype=torch.float32)
+    if N:
+        check(lib().rohm_smplx_joints(nat.handle, ptr(pose), 22, ptr(betas), ptr(transl), N, ptr(out), 22, stream_ptr(pose.device)),
+              'rohm_smplx_joints')
+    return out
+
+
+def export_params(repr, transf, body_model, clip_len=None, overlap_len=2, frame='scene', cam2world=None, betas='frame',
+                  stats=None, keep='first', plan=None, device=None):
+    """Representation rows -> an `ExportResult` of per-frame SMPL-X parameters in scene or camera coordinates.
+
+    repr: [C, T, 294] or the networks' [C, 294, 1, T] (read in place), a device tensor straight from
+    `prox_egobody_results` / `run_prox_iterations` or an array from a pickle; `stats` = (mean, std) or a dataset with Mean / Std
+    when it is still normalised.  transf [C, 4, 4]: scene -> canonical (`trans_scene2cano_list`, `transf_matrix`), None for
+    clips that stay in their canonical frame.  frame='camera' applies inv(cam2world) after the way back to the scene.
+    clip_len defaults to T + 1 (the loaders' clips); `plan` = (frame_clip, frame_t) overrides `plan_frames`.
+    betas='mean' exports the recording's mean shape for every frame (not what the reference does: it keeps per-frame shapes)."""
+    if frame not in ('scene', 'camera'):
+        raise ValueError(f"frame must be 'scene' or 'camera', got {frame!r}")
+    if betas not in ('frame', 'mean'):
+        raise ValueError(f"betas must be 'frame' or 'mean', got {betas!r}")
+    if frame == 'camera' and cam2world is None:
+        raise ValueError("frame='camera' needs cam2world")
+    if device is None:
+        device = repr.device if torch.is_tensor(repr) and repr.is_cuda else body_model.v_template.device
+    device = torch.device(device)
+    nat = native_for(body_model, device)
+    device = nat.device
+    x = _device_f32(repr, device)
+    layout, C, T = _layout(x)
+    tf = None if transf is None else _device_f32(transf, device).reshape(C, 4, 4).contiguous()
+    rigid = None
+    if frame == 'camera':
+        inv = np.linalg.inv(np.asarray(cam2world.detach().cpu() if torch.is_tensor(cam2world) else cam2world, dtype=np.float64))
+        rigid = torch.from_numpy(np.ascontiguousarray(inv.reshape(4, 4))).to(device)
+    if plan is None:
+        plan = plan_frames(C, T, T + 1 if clip_len is None else clip_len, overlap_len, keep)[:2]
+    fc = torch.as_tensor(np.asarray(plan[0], dtype=np.int32)).to(device) if not torch.is_tensor(plan[0]) else plan[0].to(device, torch.int32)
+    ft = torch.as_tensor(np.asarray(plan[1], dtype=np.int32)).to(device) if not torch.is_tensor(plan[1]) else plan[1].to(device, torch.int32)
+    fc, ft = fc.contiguous(), ft.contiguous()
+    mean = std = None
+    if stats is not None:
+        from .data_loaders.motion_representation import _stats
+        mean, std = _stats(stats, device)
+    if betas == 'mean' and fc.numel():
+        # the kernel must see the mean shape: de-normalise once (rohm_result_rows: the same two float32 operations), overwrite
+        from .drivers.results import result_rows
+        if mean is not None:
+            x = result_rows([(x, layout)], stats)[0]
+        else:
+            x = (x if layout == 'btc' else x[:, :, 0].permute(0, 2, 1)).contiguous().clone()
+        layout, mean, std = 'btc', None, None
+        ok = (fc >= 0) & (fc < C) & (ft >= 0) & (ft < T)
+        rows = x[fc[ok].long(), ft[ok].long(), 280:290]
+        x[:, :, 280:290] = rows.double().mean(dim=0).float()
+    params, contact = ops.export_smplx(nat.handle, x, layout, fc, ft, transf=tf, rigid=rigid, mean=mean, std=std)
+    res = ExportResult(params, None, contact, fc, ft, frame)
+    res.joints = _joints(nat, res.pose_f32(), res.betas.float().contiguous(), res.transl.float().contiguous())
+    return res
+
+
+def _vertex_chunks(result, body_model, every=1, chunk=256):
+    """Yields (frame indices, verts [n, V, 3] float32 device tensor) over the frames 0, every, 2 every, ..."""
+    nat = native_for(body_model, result.params79.device)
+    idx = torch.arange(0, len(result), max(int(every), 1), device=result.params79.device)
+    pose, be, tr = result.pose_f32(), result.betas.float(), result.transl.float()
+    for a in range(0, idx.numel(), chunk):
+        sel = idx[a:a + chunk]
+        _, verts = lbs_forward(nat, pose[sel].contiguous(), 0, be[sel].contiguous(), tr[sel].contiguous())
+        yield sel, verts
+
+
+def export_vertices(result, body_model, every=1, chunk=256):
+    """Vertices [ceil(N / every), V, 3] (float32, device) of every `every`-th exported frame: `rohm_smplx_forward` with
+    axis-angle poses on the exported parameters, in chunks -- already in the export's coordinate frame."""
+    parts = [v for _, v in _vertex_chunks(result, body_model, every, chunk)]
+    if not parts:
+        nat = native_for(body_model, result.params79.device)
+        return torch.empty(0, nat.num_verts, 3, device=result.params79.device, dtype=torch.float32)
+    return torch.cat(parts, dim=0)
+
+
+# ---- writers (host) ----------------------------------------------------------------------------------------------------------
+def _host(t, dtype=None):
+    a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    return a if dtype is None else a.astype(dtype)
+
+
+def _names(frame_names, n):
+    names = [str(s) for s in frame_names]
+    if len(names) < n:
+        raise ValueError(f'{n} frames but {len(names)} frame names')
+    return names[:n]
+
+
+def write_npz(path, result, frame_names):
+    """One smplx_params.npz per recording: global_orient / transl / betas / body_pose (float32), joints, foot_contact,
+    frame_names, frame_clip, coordinate_frame, gender."""
+    p = _host(result.params79)
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    out = {k: p[:, a:b].astype(np.float32) for k, (a, b) in PARAM_COLS.items()}
+    np.savez(path, joints=_host(result.joints, np.float32), foot_contact=_host(result.contact, np.float32),
+             frame_names=np.array(_names(frame_names, len(p))), frame_clip=_host(result.frame_clip, np.int32),
+             coordinate_frame=np.str_(result.coordinate_frame), gender=np.str_('neutral'), **out)
+    return path
+
+
+def write_prox_fits(root, recording, result, frame_names, body_idx=None):
+    """<root>/<recording>/results/<frame>/000.pkl (EgoBody's layout with `body_idx`: <root>/<recording>/body_idx_<k>/results/...)
+    with the keys the loaders read -- transl, global_orient, betas, body_pose, each [1, k] float32 -- and zero jaw_pose,
+    leye_pose, reye_pose, expression.  The loaders expect camera coordinates: export with frame='camera'."""
+    p = _host(result.params79).astype(np.float32)
+    base = os.path.join(root, recording) if body_idx is None else os.path.join(root, recording, f'body_idx_{body_idx}')
+    zeros = {'jaw_pose': 3, 'leye_pose': 3, 'reye_pose': 3, 'expression': 10}
+    for i, name in enumerate(_names(frame_names, len(p))):
+        d = os.path.join(base, 'results', name)
+        os.makedirs(d, exist_ok=True)
+        row = {k: p[i:i + 1, a:b].copy() for k, (a, b) in PARAM_COLS.items()}
+        row.update({k: np.zeros((1, n), np.float32) for k, n in zeros.items()})
+        with open(os.path.join(d, '000.pkl'), 'wb') as f:
+            pickle.dump(row, f, protocol=2)
+    return os.path.join(base, 'results')
+
+
+def write_ply(path, verts, faces):
+    """Binary little-endian PLY (float x y z, uchar-counted int faces) that `rohm_amd.occlusion.read_ply` reads back."""
+    v = np.ascontiguousarray(_host(verts), dtype='<f4').reshape(-1, 3)
+    f = np.asarray(_host(faces)).reshape(-1, 3)
+    rec = np.zeros(len(f), dtype=np.dtype([('n', 'u1'), ('v', '<i4', (3,))]))
+    rec['n'], rec['v'] = 3, f
+    head = ('ply\nformat binary_little_endian 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\n'
+            'element face {}\nproperty list uchar int vertex_indices\nend_header\n').format(len(v), len(f))
+    with open(path, 'wb') as out:
+        out.write(head.encode('ascii'))
+        out.write(v.tobytes())
+        out.write(rec.tobytes())
+    return path
+
+
+def write_obj(path, verts, faces):
+    v = _host(verts).reshape(-1, 3)
+    f = np.asarray(_host(faces)).reshape(-1, 3) + 1
+    with open(path, 'w') as out:
+        out.writelines('v {:.8g} {:.8g} {:.8g}\n'.format(*r) for r in v.tolist())
+        out.writelines('f {} {} {}\n'.format(*r) for r in f.tolist())
+    return path
+
+
+def write_meshes(out_dir, result, body_model, frame_names, mesh_interval=1, fmt='ply', chunk=256):
+    """meshes/<frame>.ply (or .obj) for every `mesh_interval`-th frame; one device-to-host copy per chunk of meshes."""
+    faces = getattr(body_model, 'faces', None)
+    if faces is None:
+        raise _lib.RohmHipError("meshes need the body model's faces (SMPLXLayer.from_npz keeps them)")
+    faces = np.asarray(faces).astype(np.int32).reshape(-1, 3)
+    names = _names(frame_names, len(result))
+    d = os.path.join(out_dir, 'meshes')
+    os.makedirs(d, exist_ok=True)
+    write = write_ply if fmt == 'ply' else write_obj
+    n = 0
+    for sel, verts in _vertex_chunks(result, body_model, mesh_interval, chunk):
+        host = verts.cpu().numpy()
+        for i, v in zip(sel.tolist(), host):
+            write(os.path.join(d, f'{names[i]}.{fmt}'), v, faces)
+            n += 1
+    return n
+
+
+# ---- the tool -----------------------------------------------------------------------------------------------------------------
+def build_parser():
+    ap = argparse.ArgumentParser(prog='python -m rohm_amd.export',
+                                 description='SMPL-X parameters and meshes of a reconstruction, in scene or camera coordinates')
+    ap.add_argument('--dataset', choices=['prox', 'egobody', 'amass'], default='prox')
+    ap.add_argument('--saved_data_dir', type=str, default='', help='directory of the drivers\' <recording>.pkl files')
+    ap.add_argument('--saved_data_path', type=str, default='', help='one result pickle')
+    ap.add_argument('--recordings', type=str, default='', help='comma-separated recording names (default: every pickle of the directory)')
+    ap.add_argument('--dataset_root', type=str, default='', help='PROX / EgoBody root (calibration; needed for --frame camera)')
+    ap.add_argument('--body_model_path', type=str, default='body_models/smplx_model')
+    ap.add_argument('--out', type=str, default='exported')
+    ap.add_argument('--frame', choices=['scene', 'camera'], default='scene')
+    ap.add_argument('--formats', type=str, default='npz', help='comma-separated: npz, prox_fits')
+    ap.add_argument('--meshes', choices=['none', 'ply', 'obj'], default='none')
+    ap.add_argument('--mesh_interval', type=int, default=1)
+    ap.add_argument('--keep', choices=['first', 'last'], default='first')
+    ap.add_argument('--betas', choices=['frame', 'mean'], default='frame')
+    ap.add_argument('--overlap_len', type=int, default=2)
+    ap.add_argument('--clip_len', type=int, default=0, help='frames per loader clip; 0 = rows per clip + 1.  The drivers\' pose '
+                    'stage keeps clip_len - 2 rows: give their --clip_len for their pickles')
+    ap.add_argument('--init_root', type=str, default='', help='initial fits: frame names come from its sorted listing')
+    ap.add_argument('--device', type=str, default='cuda:0')
+    return ap
+
+
+def parse_args(argv=None):
+    args = build_parser().parse_args(argv)
+    args.formats = [s for s in args.formats.split(',') if s]
+    bad = [s for s in args.formats if s not in FORMATS]
+    if bad:
+        raise SystemExit(f'--formats: unknown {bad}; choose from {list(FORMATS)}')
+    args.recordings = [s for s in args.recordings.split(',') if s]
+    if bool(args.saved_data_dir) == bool(args.saved_data_path):
+        raise SystemExit('give one of --saved_data_dir and --saved_data_path')
+    if args.frame == 'camera' and (args.dataset == 'amass' or not args.dataset_root):
+        raise SystemExit('--frame camera needs --dataset prox|egobody and --dataset_root (the calibration files)')
+    return args
+
+
+def _pickles(args):
+    if args.saved_data_path:
+        return [args.saved_data_path]
+    if args.recordings:
+        return [os.path.join(args.saved_data_dir, r + '.pkl') for r in args.recordings]
+    return sorted(os.path.join(args.saved_data_dir, n) for n in os.listdir(args.saved_data_dir) if n.endswith('.pkl'))
+
+
+def _frame_names(args, recording, info, n):
+    if args.init_root and args.dataset in ('prox', 'egobody'):
+        sub = (recording, 'results') if args.dataset == 'prox' else (recording, f"body_idx_{info['body_idx']}", 'results')
+        names = sorted(os.listdir(os.path.join(args.init_root, *sub)))
+        if len(names) >= n:
+            return names[:n]
+        print(f'[rohm_amd.export] {recording}: {len(names)} frame folders for {n} frames, numbering them instead')
+    return ['frame_%05d' % i for i in range(n)]
+
+
+def _export_one(args, path, body, device):
+    with open(path, 'rb') as f:
+        data = pickle.load(f, encoding='latin1')
+    rec = np.asarray(data['motion_repr_rec_list'], dtype=np.float32)
+    n_written = 0
+    if args.dataset == 'amass':
+        T = rec.shape[1]
+        base = os.path.splitext(os.path.basename(path))[0]
+        rec = torch.from_numpy(rec).to(device)
+        for c in range(rec.shape[0]):
+            plan = (np.full(T, c, np.int32), np.arange(T, dtype=np.int32))
+            res = export_params(rec, None, body, frame='scene', betas=args.betas, plan=plan, device=device)
+            out = os.path.join(args.out, base, 'seq_%03d' % c)
+            names = ['frame_%05d' % i for i in range(T)]
+            n_written += _write(args, out, 'seq_%03d' % c, res, body, names, None)
+        return n_written
+    recording = str(data.get('recording_name') or os.path.splitext(os.path.basename(path))[0])
+    transf = np.asarray(data['trans_scene2cano_list'], dtype=np.float32)
+    keep_rows = first_pass_rows(transf)
+    if keep_rows < len(transf):
+        print(f'[rohm_amd.export] {recording}: rows {keep_rows}..{len(transf) - 1} repeat the first batch, dropped')
+        rec, transf = rec[:keep_rows], transf[:keep_rows]
+    info, cam2world = None, None
+    if args.dataset == 'egobody' and args.dataset_root:
+        from .data_loaders.dataloader_video import read_egobody_info
+        info = read_egobody_info(args.dataset_root, recording)
+    if args.frame == 'camera':
+        from .data_loaders.dataloader_video import read_cam2world
+        cam2world = read_cam2world(args.dataset, args.dataset_root, recording, info)
+    T = rec.shape[1]
+    res = export_params(rec, transf, body, clip_len=args.clip_len or T + 1, overlap_len=args.overlap_len, frame=args.frame,
+                        cam2world=cam2world, betas=args.betas, keep=args.keep, device=device)
+    if args.dataset == 'egobody' and info is None and (args.init_root or 'prox_fits' in args.formats):
+        raise SystemExit('EgoBody frame names and fit folders need --dataset_root (egobody_rohm_info.csv)')
+    names = _frame_names(args, recording, info, len(res))
+    return _write(args, os.path.join(args.out, recording), recording, res, body, names, info)
+
+
+def _write(args, out, recording, res, body, names, info):
+    os.makedirs(out, exist_ok=True)
+    if 'npz' in args.formats:
+        write_npz(os.path.join(out, 'smplx_params.npz'), res, names)
+    if 'prox_fits' in args.formats:
+        write_prox_fits(os.path.join(out, 'fits'), recording, res, names, body_idx=info['body_idx'] if info else None)
+    n_mesh = 0
+    if args.meshes != 'none':
+        n_mesh = write_meshes(out, res, body, names, args.mesh_interval, args.meshes)
+    print(f'[rohm_amd.export] {recording}: {len(res)} frames ({res.coordinate_frame}), {n_mesh} meshes -> {out}')
+    return len(res)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from .data_loaders.dataloader_video import _body_model
+    device = torch.device(args.device)
+    body = _body_model(args.body_model_path, 'neutral', device)
+    total = sum(_export_one(args, p, body, device) for p in _pickles(args))
+    print(f'[rohm_amd.export] {total} frames exported')
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -182,3 +182,38 @@ def ddpm_step_table(x_t, x0, noise, tables, t, grad_a=None, w_a=0.0, grad_b=None
                                      ptr(tables), ptr(t), tables.shape[0], ptr(out), B, x_t.numel() // B,
                                      stream_ptr(x_t.device)), 'rohm_ddpm_step_table')
     return out
+
+
+def export_smplx(handle, repr_full, layout, frame_clip, frame_t, transf=None, rigid=None, mean=None, std=None, want_contact=True):
+    """rohm_export_smplx (include/rohm_hip.h): rows of the 294-channel representation -> (params [N, 79] float64 in the
+    smplx_world layout global_orient 3, transl 3, betas 10, body_pose 63; contact [N, 4] float32 or None).
+
+    `handle`: the body model's native handle (body_model.native_for(...).handle).  `repr_full`: float32 [C, T, 294]
+    (layout 'btc') or [C, 294, 1, T] ('bc1t'), read in place through its strides.  `frame_clip` / `frame_t`: int32 [N]
+    device tensors, the clip and row every output frame is gathered from (out of range -> a NaN row).  `transf` [C, 4, 4]
+    float32 (scene -> canonical, inverted on the device), `rigid` [4, 4] float64 (applied after the inverse), `mean` / `std`
+    float32 [294] (both or neither) may be None."""
+    _lib.require_hip(repr_full, frame_clip, frame_t, transf, rigid, mean, std)
+    if repr_full.dtype != torch.float32:
+        raise TypeError('export_smplx reads a float32 representation')
+    if layout == 'btc' and repr_full.dim() == 3 and repr_full.shape[2] == 294:
+        n_clip, T, sb, st, sc = repr_full.shape[0], repr_full.shape[1], repr_full.stride(0), repr_full.stride(1), repr_full.stride(2)
+    elif layout == 'bc1t' and repr_full.dim() == 4 and repr_full.shape[1] == 294 and repr_full.shape[2] == 1:
+        n_clip, T, sb, st, sc = repr_full.shape[0], repr_full.shape[3], repr_full.stride(0), repr_full.stride(3), repr_full.stride(1)
+    else:
+        raise ValueError(f"expected [C, T, 294] ('btc') or [C, 294, 1, T] ('bc1t'), got {tuple(repr_full.shape)} as {layout!r}")
+    if frame_clip.dtype != torch.int32 or frame_t.dtype != torch.int32 or frame_clip.shape != frame_t.shape or frame_clip.dim() != 1:
+        raise ValueError('frame_clip and frame_t must be int32 [N]')
+    if (mean is None) != (std is None):
+        raise ValueError('pass both mean and std or neither')
+    for name, t, shape, dt in (('transf', transf, (n_clip, 4, 4), torch.float32), ('rigid', rigid, (4, 4), torch.float64),
+                               ('mean', mean, (294,), torch.float32), ('std', std, (294,), torch.float32)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dt):
+            raise ValueError(f'{name} must be {dt} {list(shape)}, got {t.dtype} {list(t.shape)}')
+    N, dev = frame_clip.numel(), repr_full.device
+    params = torch.empty(N, 79, device=dev, dtype=torch.float64)
+    contact = torch.empty(N, 4, device=dev, dtype=torch.float32) if want_contact else None
+    check(lib().rohm_export_smplx(handle, C.c_void_p(repr_full.data_ptr()), sb, st, sc, ptr(mean), ptr(std), ptr(transf), ptr(rigid),
+                                  ptr(frame_clip), ptr(frame_t), n_clip, T, N, ptr(params), ptr(contact), stream_ptr(dev)),
+          'rohm_export_smplx')
+    return params, contact
