@@ -918,6 +918,25 @@ int rohm_export_smplx(const rohm_smplx_t* h, const float* repr, long long in_str
                       const double* rigid, const int* frame_clip, const int* frame_t, int C, int T, int N,
                       double* params, float* contact, rohm_stream_t stream);
 
+/* A track of per-frame SMPL-X estimates at any frame rate, with frames that have no fit, resampled to the times
+ * times_dst [n_out] (the 30 fps grid of the networks, or a reconstruction back onto the source's time stamps).  No
+ * counterpart in the reference.  All arrays are device memory: times_src [N] float64 seconds, strictly increasing;
+ * valid_idx [Nv] int32, the ascending indices of the source frames that have a fit (read back and checked here: one stream
+ * synchronisation per call); params [N,79] float64 (global_orient 3, transl 3, betas 10, body_pose 63); keypoints [N,J,3]
+ * float32 (x, y, confidence; J = 0 and NULL allowed); mask_joint [N,M] float32 (M = 0 and NULL allowed).
+ * For an output time t: i0 = last valid frame with times_src <= t, i1 = first valid frame with times_src >= t; where one
+ * side does not exist both are the nearest valid frame and gap = 1; alpha = (t - t0) / (t1 - t0) in float64, 0 when
+ * i0 == i1; gap = 1 also when t1 - t0 > max_gap (seconds).  alpha == 0 copies the bits of source row i0.  Otherwise the 22
+ * rotations are float64 quaternion slerps (shortest arc, lerp weights when sin(omega) < 1e-8, |rotation vector| <= pi),
+ * transl and betas are a + alpha (b - a) -- inside a gap too.  Keypoints outside a gap: confidence min(c0, c1), x / y
+ * interpolated in float64 and stored as float32, taken from the other bracket where one confidence is 0; mask min(m0, m1).
+ * Inside a gap keypoints and mask are 0.  src_index [n_out] = i0, gap [n_out] uint8.  No atomics: the same input gives
+ * the same bits.  n_out == 0 returns without a launch. */
+int rohm_track_resample(const double* times_src, const int32_t* valid_idx, const double* params, const float* keypoints,
+                        const float* mask_joint, const double* times_dst, double max_gap, int N, int Nv, int J, int M,
+                        int n_out, double* params_out, float* keypoints_out, float* mask_out, int32_t* src_index,
+                        unsigned char* gap, rohm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

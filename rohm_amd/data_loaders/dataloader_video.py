@@ -175,6 +175,12 @@ def _floor_table(dataset, floor_heights, rohm_root):
     return None
 
 
+def _dev32(x, device):
+    if torch.is_tensor(x):
+        return x.to(device=device, dtype=torch.float32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(device)
+
+
 def _body_model(body_model_path, gender, device):
     """An injected nn.Module (used for every gender), an SMPLX_*.npz file, or a model directory."""
     from ..body_model import SMPLXLayer
@@ -201,13 +207,32 @@ class DataloaderVideo(data.Dataset):
                  logdir=None, device='cuda', floor_heights=None, rohm_root=None):
         if dataset not in ('prox', 'egobody'):
             raise ValueError(f'dataset {dataset!r} not defined')
+        self._setup(dataset, task, repr_abs_only, clip_len, overlap_len, joints_num, logdir, device, use_scene_floor_height)
+        self.init_root, self.base_dir, self.recording_name = init_root, base_dir, recording_name
+        self.up_axis, self.undistort, self.image_width = ('z', True, 1920) if dataset == 'prox' else ('y', False, 1920)
+
+        read = read_prox_recording if dataset == 'prox' else read_egobody_recording
+        rec = read(init_root, base_dir, recording_name, joints_num)
+        self._camera(rec)
+        if dataset == 'egobody':
+            self.view, self.body_idx, self.gender_gt = rec['view'], rec['body_idx'], rec['gender_gt']
+            self.fitting_gt_root = rec['fitting_gt_root']
+        table = _floor_table(dataset, floor_heights, rohm_root)
+        self.scene_floor_height = table[self.scene_name] if table is not None else None
+        if use_scene_floor_height and self.scene_floor_height is None:
+            raise ValueError('use_scene_floor_height needs floor_heights= or rohm_root=')
+        self._stats_and_model(logdir, body_model_path)
+        self._build(rec, body_model_path)
+
+    def _setup(self, dataset, task, repr_abs_only, clip_len, overlap_len, joints_num, logdir, device, use_scene_floor_height):
+        """What does not depend on where the recording comes from (data_loaders/track.py starts here too)."""
         if task not in ('traj', 'pose'):
             raise ValueError("task should be in ['traj', 'pose']")
         if joints_num != 22:
             raise ValueError('the motion representation is defined for joints_num = 22')
         self.dataset, self.task, self.repr_abs_only = dataset, task, repr_abs_only
         self.clip_len, self.clip_overlap_len, self.joints_num = clip_len, overlap_len, joints_num
-        self.init_root, self.base_dir, self.logdir, self.recording_name = init_root, base_dir, logdir, recording_name
+        self.logdir = logdir
         self.use_scene_floor_height = use_scene_floor_height
         self.device = torch.device(device)
         if self.device.type != 'cuda':
@@ -224,38 +249,32 @@ class DataloaderVideo(data.Dataset):
         self.traj_feat_dim = sum(REPR_DIM_DICT[k] for k in self.traj_repr_name_list)
         self.pose_feat_dim = sum(REPR_DIM_DICT[k] for k in self.local_repr_name_list)
 
-        read = read_prox_recording if dataset == 'prox' else read_egobody_recording
-        rec = read(init_root, base_dir, recording_name, joints_num)
+    def _camera(self, rec):
         self.scene_name, self.color_cam = rec['scene_name'], rec['color_cam']
         # dataloader_video.py:102-104, :252-254: what PoseNet's 2-D guidance reads of its dataset (posenet.py:296)
         cam2world = torch.from_numpy(np.asarray(rec['cam2world'], dtype=np.float64)).float().to(self.device)
         self.cam_R, self.cam_t = cam2world[:3, :3].reshape([3, 3]), cam2world[:3, 3].reshape([1, 3])
-        if dataset == 'egobody':
-            self.view, self.body_idx, self.gender_gt = rec['view'], rec['body_idx'], rec['gender_gt']
-            self.fitting_gt_root = rec['fitting_gt_root']
-        table = _floor_table(dataset, floor_heights, rohm_root)
-        self.scene_floor_height = table[self.scene_name] if table is not None else None
-        if use_scene_floor_height and self.scene_floor_height is None:
-            raise ValueError('use_scene_floor_height needs floor_heights= or rohm_root=')
+
+    def _stats_and_model(self, logdir, body_model_path):
         self.Mean_dict, self.Std_dict, self.Mean, self.Std = read_stats(logdir)
         self.smplx_neutral = _body_model(body_model_path, 'neutral', self.device)
-        self._build(rec, body_model_path)
 
-    def _build(self, rec, body_model_path):
+    def _build(self, rec, body_model_path, starts=None):
+        """rec['params'] / ['keypoints'] / ['mask_joint'] are host arrays or device tensors; `starts`: explicit window starts
+        (data_loaders/track.py) instead of the reference's windows."""
         dev, L, ov = self.device, self.clip_len, self.clip_overlap_len
         n_frames = len(rec['frame_names'])
         joints_world, smplx_world = frames.frames_to_world(self.smplx_neutral, rec['params'], rec['cam2world'], dev)
-        built = clips.build_clips(joints_world, smplx_world, L, ov, up_axis='z' if self.dataset == 'prox' else 'y',
+        built = clips.build_clips(joints_world, smplx_world, L, ov, up_axis=self.up_axis, starts=starts,
                                   preset_floor_height=self.scene_floor_height if self.use_scene_floor_height else None,
                                   stats=(self.Mean, self.Std))
         n = self.n_samples = int(built['repr'].shape[0])
         idx = built['starts'].long()[:, None] + torch.arange(L, device=dev)[None]                  # [C, L] frame indices
         kp_host = rec['keypoints'][:, 0:self.joints_num]
-        kp = torch.from_numpy(np.ascontiguousarray(kp_host, dtype=np.float32)).to(dev)
-        mask = torch.from_numpy(np.ascontiguousarray(rec['mask_joint'][:n_frames], dtype=np.float32)).to(dev)
-        joint_vis, vec_vis = clips.visibility_masks(kp, mask, L, ov)
-        if self.dataset == 'prox':
-            kp = clips.undistort_keypoints(kp, self.color_cam['camera_mtx'], self.color_cam['k'])
+        kp, mask = _dev32(kp_host, dev), _dev32(rec['mask_joint'][:n_frames], dev)
+        joint_vis, vec_vis = clips.visibility_masks(kp, mask, L, ov, starts=starts)
+        if self.undistort:
+            kp = clips.undistort_keypoints(kp, self.color_cam['camera_mtx'], self.color_cam['k'], self.image_width)
         f32 = dict(device=dev, dtype=torch.float32)
         focal = torch.tensor([self.color_cam['f'][0], self.color_cam['f'][1]], **f32)
         center = torch.tensor([self.color_cam['c'][0], self.color_cam['c'][1]], **f32)

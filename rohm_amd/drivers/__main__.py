@@ -1,4 +1,4 @@
-"""`python -m rohm_amd.drivers amass_full|prox_egobody|posenet|trajnet [--config cfg.yaml] [--key value ...]`: the reference's
+"""`python -m rohm_amd.drivers amass_full|prox_egobody|posenet|trajnet|track [--config cfg.yaml] [--key value ...]`: the reference's
 test_amass_full.py / test_prox_egobody.py / test_posenet.py / test_trajnet.py on the native loaders, networks, samplers and
 result tails (rohm_amd.drivers.results).
 
@@ -11,6 +11,10 @@ rohm_amd.evaluation), `--eval_noise_root` (amass_full: the directory of smplx_no
 evaluation lines straight from the device results).  Out of scope: sharding a driver over several GPUs (rohm_amd.sharding does that
 from Python), the open3d viewers (`--visualize` is accepted and prints one line; pictures come from `rohm_amd.evaluation --render`) and the
 reference's DataLoader worker processes.
+
+`track` has no script behind it: it is `prox_egobody` on a generic track file (rohm_amd.data_loaders.track) -- `--track file.npz`
+instead of `--dataset`, `--init_root`, `--dataset_root`, `--recording_name`, `--rohm_root` and `--floor_heights`, plus `--tail
+cover|drop` and `--max_gap SECONDS`.
 """
 from __future__ import annotations
 
@@ -62,19 +66,24 @@ TRAJNET = _HEAD + [('diffusion_steps', 100, int)] + _SCHEDULE + [
     ('noise_std_smplx_trans', 0.01, float), ('noise_std_smplx_betas', 0.1, float),
     ('batch_size', 64, int), ('infill_traj', False, _bool), ('max_infill_ratio', 0.1, float), ('visualize', True, _bool)]
 SPECS = {'amass_full': AMASS_FULL, 'prox_egobody': PROX_EGOBODY, 'posenet': POSENET, 'trajnet': TRAJNET}
+# prox_egobody's arguments without the directory layout; the save root is the package's choice
+TRACK = [(n, 'test_results/results_track' if n == 'save_root' else d, t) for n, d, t in PROX_EGOBODY
+         if n not in ('dataset', 'dataset_root', 'init_root', 'recording_name')]
 # the package's own arguments (everything above is the scripts')
 _SAVE = [('save_interval', 0, int), ('evaluate', False, _bool)]
 OWN = {'amass_full': [('eval_noise_root', 'data/eval_noise_smplx', str)] + _SAVE,
        'prox_egobody': [('rohm_root', '', str), ('floor_heights', '', str)] + _SAVE,
-       'posenet': _SAVE, 'trajnet': [('evaluate', False, _bool)]}
+       'posenet': _SAVE, 'trajnet': [('evaluate', False, _bool)],
+       'track': [('track', '', str), ('tail', 'cover', str), ('max_gap', None, lambda s: None if s in ('', 'None', 'none') else float(s))]
+       + _SAVE}
 CHOICES = {'noise_schedule': ['linear', 'cosine'], 'task': ['traj', 'pose'], 'mask_scheme': ['lower', 'upper', 'full'],
-           'dataset': ['prox', 'egobody']}
-USAGE = 'usage: python -m rohm_amd.drivers amass_full|prox_egobody|posenet|trajnet [--config cfg.yaml] [--key value ...]'
+           'dataset': ['prox', 'egobody'], 'tail': ['cover', 'drop']}
+USAGE = 'usage: python -m rohm_amd.drivers amass_full|prox_egobody|posenet|trajnet|track [--config cfg.yaml] [--key value ...]'
 
 
 def parse_args(which, argv):
     """Namespace of the driver's arguments: defaults, then the config file's values, then the command line's."""
-    spec = SPECS[which] + OWN[which]
+    spec = (TRACK if which == 'track' else SPECS[which]) + OWN[which]
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument('--config', default='')
     known, _ = pre.parse_known_args(argv)
@@ -300,6 +309,47 @@ def main_prox_egobody(args):
     return {'path': path, 'lines': lines, 'report': report}
 
 
+# ---- a generic track ------------------------------------------------------------------------------------------------------------------
+def main_track(args):
+    """`main_prox_egobody` on two `DataloaderTrack`s.  The pickle has the scripts' keys plus what `rohm_amd.export --dataset track`
+    needs to put the reconstruction back on the source's time stamps: times_dst, src_index, gap (per 30 fps frame), clip_starts,
+    times_src, valid, source_frame_names and cam2world."""
+    from ..data_loaders.track import DataloaderTrack, read_track
+    from ..inference import run_prox_iterations
+    from . import results as R
+    if args.evaluate:
+        raise ValueError('--evaluate is not available for tracks: there is no ground truth, and the scene metrics are defined for '
+                         'PROX and EgoBody only')
+    if not args.track:
+        raise ValueError('give --track file.npz')
+    device = f'cuda:{args.device}'
+    print("creating data loader...")
+    track = read_track(args.track)
+    if args.cond_fn_with_grad and not track['has_keypoints']:
+        raise ValueError('--cond_fn_with_grad True guides PoseNet with the 2-D keypoints: the track needs keypoints_2d and the '
+                         'camera (focal_length and camera_center, or camera_mtx with dist_coeffs); run with --cond_fn_with_grad False')
+    body = _make_body_model(args.body_model_path, device)
+    kw = dict(body_model_path=body, use_scene_floor_height=args.use_scene_floor_height, clip_len=args.clip_len,
+              overlap_len=args.window_size, tail=args.tail, max_gap=args.max_gap, device=device)
+    pose_dataset = DataloaderTrack(track, task='pose', logdir=_logdir(args.model_path_posenet), **kw)
+    traj_dataset = DataloaderTrack(track, task='traj', repr_abs_only=args.repr_abs_only, logdir=_logdir(args.model_path_trajnet), **kw)
+    models, diffusions = _two_stage(args, pose_dataset, traj_dataset, body, device)
+    extra = {'times_dst': pose_dataset.times_dst, 'src_index': pose_dataset.src_index, 'gap': pose_dataset.gap,
+             'clip_starts': np.asarray(pose_dataset.clip_starts), 'times_src': pose_dataset.times_src, 'valid': pose_dataset.valid,
+             'source_frame_names': np.asarray(track['frame_names']), 'cam2world': np.asarray(track['cam2world'])}
+    static = dict(R.repr_static(), recording_name=pose_dataset.recording_name, **extra)
+    args.dataset = 'track'
+    writer = R.ResultWriter(R.prox_egobody_pickle_path(args, pose_dataset.recording_name), R.SCENE_PICKLE_KEYS + list(extra), static,
+                            last_only=('frame_name_list',), save_interval=args.save_interval)
+    for batch_pose, batch_traj in _scheduled(pose_dataset, traj_dataset, args.batch_size, lambda ds: ds.batches(args.batch_size)):
+        val_output_joint, _, _ = run_prox_iterations(args, models, diffusions, batch_traj, batch_pose, traj_dataset, pose_dataset, body)
+        writer.add(R.prox_egobody_results(val_output_joint, batch_pose, pose_dataset, body, 'prox'))
+        print('current data saved.')
+    path = writer.close()
+    print('test finished.')
+    return {'path': path, 'lines': []}
+
+
 # ---- test_posenet.py ----------------------------------------------------------------------------------------------------------------
 def _amass_dataset(args, body, device, **kw):
     from ..data_loaders.dataloader_amass import DataloaderAMASS
@@ -399,12 +449,13 @@ def main_trajnet(args):
     return {'path': None, 'lines': lines, 'report': report}
 
 
-MAINS = {'amass_full': main_amass_full, 'prox_egobody': main_prox_egobody, 'posenet': main_posenet, 'trajnet': main_trajnet}
+MAINS = {'amass_full': main_amass_full, 'prox_egobody': main_prox_egobody, 'posenet': main_posenet, 'trajnet': main_trajnet,
+         'track': main_track}
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    if not argv or argv[0] not in SPECS:
+    if not argv or argv[0] not in MAINS:
         raise SystemExit(USAGE)
     args = parse_args(argv[0], argv[1:])
     fixseed(args.seed)

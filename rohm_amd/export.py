@@ -73,9 +73,10 @@ class ExportResult:
     """Device tensors of an exported track: params79 [N, 79] float64 (global_orient 3, transl 3, betas 10, body_pose 63) and its
     four views, joints [N, 22, 3] float32, contact [N, 4] float32, frame_clip / frame_t int32 [N], coordinate_frame."""
 
-    def __init__(self, params79, joints, contact, frame_clip, frame_t, coordinate_frame):
+    def __init__(self, params79, joints, contact, frame_clip, frame_t, coordinate_frame, times=None, gap=None):
         self.params79, self.joints, self.contact = params79, joints, contact
         self.frame_clip, self.frame_t, self.coordinate_frame = frame_clip, frame_t, coordinate_frame
+        self.times, self.gap = times, gap          # tracks: seconds [N] float64 and "no evidence here" [N] uint8 (host arrays)
         for k, (a, b) in PARAM_COLS.items():
             setattr(self, k, params79[:, a:b])
 
@@ -164,6 +165,34 @@ def export_params(repr, transf, body_model, clip_len=None, overlap_len=2, frame=
     return res
 
 
+def resample_params(result, times_from, times_to, body_model=None, gap_from=None, max_gap=None):
+    """An exported track on other time stamps: `rohm_track_resample` (csrc/track.hip) with J = M = 0 on params79, every row of
+    `result` valid.  times_from [N]: the times of the rows of `result` (a `DataloaderTrack`'s times_dst); times_to [n]: e.g. the
+    source's own time stamps.  Rotations are slerped, transl and betas interpolated, a time that coincides with one of
+    times_from is that row's bits; contact, frame_clip and frame_t are those of the row at the left bracket.  With `body_model`
+    the joints are recomputed from the new parameters (`rohm_smplx_joints`).  The result carries `times` = times_to and `gap`
+    [n] uint8: 1 where times_to lies outside times_from (the nearest row is held), where the brackets are further apart
+    than max_gap (default 1.5 intervals of times_from) or where `gap_from` [N] is set at the left bracket."""
+    from .data_loaders.track import resample_track
+    tf = np.asarray(times_from, dtype=np.float64).reshape(-1)
+    tt = np.asarray(times_to, dtype=np.float64).reshape(-1)
+    if tf.shape[0] != len(result):
+        raise ValueError(f'{len(result)} exported rows but {tf.shape[0]} times')
+    device = result.params79.device
+    out = resample_track(tf, np.ones(tf.shape[0], bool), result.params79, None, None, tt, max_gap, device)
+    left = out['src_index'].long()
+    gap = out['gap'].cpu().numpy()
+    if gap_from is not None:
+        gap = gap | np.asarray(gap_from, dtype=np.uint8).reshape(-1)[out['src_index'].cpu().numpy()]
+    res = ExportResult(out['params'], None, result.contact[left] if result.contact is not None else None, result.frame_clip[left],
+                       result.frame_t[left], result.coordinate_frame, times=tt, gap=gap)
+    res.src_index = out['src_index']
+    if body_model is not None:
+        nat = native_for(body_model, device)
+        res.joints = _joints(nat, res.pose_f32(), res.betas.float().contiguous(), res.transl.float().contiguous())
+    return res
+
+
 def _vertex_chunks(result, body_model, every=1, chunk=256):
     """Yields (frame indices, verts [n, V, 3] float32 device tensor) over the frames 0, every, 2 every, ..."""
     nat = native_for(body_model, result.params79.device)
@@ -200,12 +229,16 @@ def _names(frame_names, n):
 
 def write_npz(path, result, frame_names):
     """One smplx_params.npz per recording: global_orient / transl / betas / body_pose (float32), joints, foot_contact,
-    frame_names, frame_clip, coordinate_frame, gender."""
+    frame_names, frame_clip, coordinate_frame, gender; for a track also times (seconds) and gap (1 = no evidence at this frame)."""
     p = _host(result.params79)
     d = os.path.dirname(path)
     if d:
         os.makedirs(d, exist_ok=True)
     out = {k: p[:, a:b].astype(np.float32) for k, (a, b) in PARAM_COLS.items()}
+    if getattr(result, 'times', None) is not None:
+        out['times'] = np.asarray(result.times, dtype=np.float64)
+    if getattr(result, 'gap', None) is not None:
+        out['gap'] = np.asarray(result.gap, dtype=np.uint8)
     np.savez(path, joints=_host(result.joints, np.float32), foot_contact=_host(result.contact, np.float32),
              frame_names=np.array(_names(frame_names, len(p))), frame_clip=_host(result.frame_clip, np.int32),
              coordinate_frame=np.str_(result.coordinate_frame), gender=np.str_('neutral'), **out)
@@ -276,7 +309,7 @@ def write_meshes(out_dir, result, body_model, frame_names, mesh_interval=1, fmt=
 def build_parser():
     ap = argparse.ArgumentParser(prog='python -m rohm_amd.export',
                                  description='SMPL-X parameters and meshes of a reconstruction, in scene or camera coordinates')
-    ap.add_argument('--dataset', choices=['prox', 'egobody', 'amass'], default='prox')
+    ap.add_argument('--dataset', choices=['prox', 'egobody', 'amass', 'track'], default='prox')
     ap.add_argument('--saved_data_dir', type=str, default='', help='directory of the drivers\' <recording>.pkl files')
     ap.add_argument('--saved_data_path', type=str, default='', help='one result pickle')
     ap.add_argument('--recordings', type=str, default='', help='comma-separated recording names (default: every pickle of the directory)')
@@ -293,6 +326,8 @@ def build_parser():
     ap.add_argument('--clip_len', type=int, default=0, help='frames per loader clip; 0 = rows per clip + 1.  The drivers\' pose '
                     'stage keeps clip_len - 2 rows: give their --clip_len for their pickles')
     ap.add_argument('--init_root', type=str, default='', help='initial fits: frame names come from its sorted listing')
+    ap.add_argument('--times', choices=['source', '30fps'], default='source',
+                    help='--dataset track: export on the source\'s own time stamps or on the 30 fps grid of the reconstruction')
     ap.add_argument('--device', type=str, default='cuda:0')
     return ap
 
@@ -306,7 +341,7 @@ def parse_args(argv=None):
     args.recordings = [s for s in args.recordings.split(',') if s]
     if bool(args.saved_data_dir) == bool(args.saved_data_path):
         raise SystemExit('give one of --saved_data_dir and --saved_data_path')
-    if args.frame == 'camera' and (args.dataset == 'amass' or not args.dataset_root):
+    if args.frame == 'camera' and args.dataset != 'track' and (args.dataset == 'amass' or not args.dataset_root):
         raise SystemExit('--frame camera needs --dataset prox|egobody and --dataset_root (the calibration files)')
     return args
 
@@ -351,6 +386,8 @@ def _export_one(args, path, body, device):
     if keep_rows < len(transf):
         print(f'[rohm_amd.export] {recording}: rows {keep_rows}..{len(transf) - 1} repeat the first batch, dropped')
         rec, transf = rec[:keep_rows], transf[:keep_rows]
+    if args.dataset == 'track':
+        return _export_track(args, data, rec, transf, recording, body, device)
     info, cam2world = None, None
     if args.dataset == 'egobody' and args.dataset_root:
         from .data_loaders.dataloader_video import read_egobody_info
@@ -365,6 +402,34 @@ def _export_one(args, path, body, device):
         raise SystemExit('EgoBody frame names and fit folders need --dataset_root (egobody_rohm_info.csv)')
     names = _frame_names(args, recording, info, len(res))
     return _write(args, os.path.join(args.out, recording), recording, res, body, names, info)
+
+
+def _export_track(args, data, rec, transf, recording, body, device):
+    """A `drivers track` pickle: the plan, the times and the camera come from the pickle itself."""
+    from .data_loaders.track import frames_plan
+    missing = [k for k in ('clip_starts', 'times_dst', 'src_index', 'gap', 'times_src', 'valid', 'source_frame_names', 'cam2world')
+               if k not in data]
+    if missing:
+        raise SystemExit(f'--dataset track: the pickle has no {missing}; it was not written by `python -m rohm_amd.drivers track`')
+    starts = np.asarray(data['clip_starts']).reshape(-1)[:len(rec)]
+    fc, ft, n = frames_plan(starts, rec.shape[1], args.keep)
+    res = export_params(rec[:len(starts)], transf[:len(starts)], body, frame=args.frame, cam2world=np.asarray(data['cam2world']),
+                        betas=args.betas, plan=(fc, ft), device=device)
+    times30, gap30 = np.asarray(data['times_dst'], dtype=np.float64)[:n], np.asarray(data['gap'], dtype=np.uint8)[:n]
+    src_names = [str(s) for s in data['source_frame_names']]
+    if args.times == '30fps':
+        res.times, res.gap = times30, gap30
+        names = [src_names[i] for i in np.asarray(data['src_index'])[:n].tolist()]          # the source frame at the left bracket
+        if len(set(names)) < len(names):
+            names = ['%s_%06d' % (s, k) for k, s in enumerate(names)]
+    else:
+        # one row per source frame between the first and the last frame that had a fit, the frames without one included; a
+        # source time after the last reconstructed row (the pose stage keeps clip_len - 2 rows) holds that row, gap = 1
+        v = np.flatnonzero(np.asarray(data['valid'], dtype=bool))
+        sel = slice(int(v[0]), int(v[-1]) + 1)
+        res = resample_params(res, times30, np.asarray(data['times_src'], dtype=np.float64)[sel], body, gap_from=gap30)
+        names = src_names[sel]
+    return _write(args, os.path.join(args.out, recording), recording, res, body, names, None)
 
 
 def _write(args, out, recording, res, body, names, info):
