@@ -29,6 +29,24 @@
  *     launches of the same handle: rohm_posenet_set_exchange, rohm_posenet_inject_exchange_fault,
  *     rohm_posenet_set_stack_timeline); calls are re-entrant across streams given distinct workspaces.
  *     One handle per device.
+ *
+ * Caller-owned memory
+ *   Every buffer the caller hands in to be written -- `ws`, `scratch`, `saved`, `buf` and every output tensor -- may hold
+ *   ANYTHING on entry: uninitialised memory, NaN, the remains of an earlier call of another shape at the same address
+ *   (a caching allocator returns the block it was just given back).  Results do not depend on those contents: what a
+ *   kernel reads it, or an earlier launch of the same call, has written; pad rows and pad columns that feed a GEMM are
+ *   cleared by the call; an exchange header without the magic word (memory the library has not armed at THAT offset) makes
+ *   the call zero the header, its statistics slots and its flags before the first launch.  tests/test_gpu_stale_memory.py
+ *   holds every entry point to this, bit for bit.  Two things are state by purpose: *_train_backward reads the `saved`
+ *   buffer *_train_forward wrote, and an armed exchange header (error word, pass counter) lives on in a workspace from
+ *   call to call.
+ *   Regions a call leaves UNWRITTEN (the caller's to initialise if it reads them):
+ *     - rohm_output_process_f32: channels outside [ch_off, ch_off + C_out) of `out`;
+ *     - rohm_traj_rederive and rohm_repr_joints_vjp address their output through strides: only the elements they name (channels
+ *       0..21 of frames 0..T-2; all 294 channels) are written, what lies between them in the caller's tensor is not touched;
+ *     - optional outputs passed as NULL are not computed; nothing else of an output tensor is skipped;
+ *     - of a workspace nothing may be read back by the caller, except where an entry point says so
+ *       (rohm_posenet_status_offset, the header words of rohm_gemm_res_layernorm_f32 / rohm_output_process_f32).
  */
 #ifndef ROHM_HIP_H
 #define ROHM_HIP_H

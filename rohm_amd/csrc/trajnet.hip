@@ -512,7 +512,8 @@ static int res_block(const rohm_trajnet* h, const ResW& r, const float* x, int l
                      int ldtb, const float* add2, int ldadd2, float* dst, int lddst, float* dst2, int lddst2,
                      const Scratch& sc, hipStream_t s) {
     int rc;
-    const int co = r.cout;
+    const int co = r.cout, ldh = hb_ld(r);
+    float* const hb = hb_buf(r, sc);      // rows as wide as the second conv's K chunks (32 channels: 64 floats, zero pad columns)
     SplitInfo s0, s1, sr, none;
     const float* tb = (r.tb_off >= 0) ? tb_all + r.tb_off : nullptr;
     // the fused forms trade flops (zero taps) for launches: only while the step is latency-bound (measured: B = 256 loses
@@ -525,10 +526,10 @@ static int res_block(const rohm_trajnet* h, const ResW& r, const float* x, int l
         static const int offs[5] = {-2, -1, 0, 1, 2};
         if ((rc = conv_gemm(h, r.b0res, x, ldx, B, T, T, 1, offs, sc.ya, 2 * co, 1, 0, s, &sf, tl_splitk_res, 0, 0, co, &sfr))) return rc;
         GnFused f0{sf, sc.ya, 2 * co}, fr{sfr, sc.ya, 2 * co};
-        if ((rc = gn(r.b0, f0.y(0), f0.ld(), f0.split(0), B, T, tb, ldtb, nullptr, 0, none, nullptr, nullptr, 0, sc.hb, co,
+        if ((rc = gn(r.b0, f0.y(0), f0.ld(), f0.split(0), B, T, tb, ldtb, nullptr, 0, none, nullptr, nullptr, 0, hb, ldh,
                      nullptr, 0, s)))
             return rc;
-        if ((rc = conv5(h, r.b1.conv, sc.hb, co, B, T, sc.rc, co, s, &s1))) return rc;
+        if ((rc = conv5(h, r.b1.conv, hb, ldh, B, T, sc.rc, co, s, &s1))) return rc;
         return gn(r.b1, sc.rc, co, s1, B, T, nullptr, 0, fr.y(co), fr.ld(), fr.split(co), r.b0res.b + co, add2, ldadd2, dst,
                   lddst, dst2, lddst2, s);
     }
@@ -539,8 +540,8 @@ static int res_block(const rohm_trajnet* h, const ResW& r, const float* x, int l
         if ((rc = conv1(r.res, x, ldx, B * T, sc.rc, co, s, &sr))) return rc;
         res = sc.rc; ldres = co;
     }
-    if ((rc = gn(r.b0, sc.ya, co, s0, B, T, tb, ldtb, nullptr, 0, none, nullptr, nullptr, 0, sc.hb, co, nullptr, 0, s))) return rc;
-    if ((rc = conv5(h, r.b1.conv, sc.hb, co, B, T, sc.ya, co, s, &s1))) return rc;
+    if ((rc = gn(r.b0, sc.ya, co, s0, B, T, tb, ldtb, nullptr, 0, none, nullptr, nullptr, 0, hb, ldh, nullptr, 0, s))) return rc;
+    if ((rc = conv5(h, r.b1.conv, hb, ldh, B, T, sc.ya, co, s, &s1))) return rc;
     return gn(r.b1, sc.ya, co, s1, B, T, nullptr, 0, res, ldres, sr, r.res.b, add2, ldadd2, dst, lddst, dst2, lddst2, s);
 }
 
@@ -558,10 +559,10 @@ static TWs carve_t(const rohm_trajnet* h, int B, int T, float* base) {
         w.cat[i] = take(Mi * 2 * ch[i]);
         w.dcat[i] = take(Mi * 2 * ch[i]);
         w.ccat[i] = take(Mi * 2 * ch[i]);
-        if (i < 3) w.cdn[i] = take((Mi / 2) * ch[i]);
+        if (i < 3) w.cdn[i] = take((Mi / 2) * pad64(ch[i]));
         w.ddn[i] = take((Mi / 2) * 2 * ch[i]);
         w.kdn[i] = take((Mi / 2) * 2 * ch[i]);
-        w.d[i] = take(Mi * (i == 0 ? kPadC : ch[i - 1]));   // d[0]: 32 channels in a 64-wide zero-padded row
+        w.d[i] = take(Mi * pad64(i == 0 ? 32 : ch[i - 1]));   // d[0] (and d[1] at mid_dim 256): 32 channels in a 64-wide zero-padded row
         w.ctrl[i] = take(Mi * (i == 0 ? 32 : ch[i - 1]));
     }
     const size_t M16 = M >> 4;
@@ -574,6 +575,7 @@ static TWs carve_t(const rohm_trajnet* h, int B, int T, float* base) {
     w.sc.ya = take(2 * (M * (m / 8) > (M >> 3) * m ? M * (m / 8) : (M >> 3) * m));     // fused [conv | residual] result
     w.sc.hb = take(M * (m / 8) > (M >> 3) * m ? M * (m / 8) : (M >> 3) * m);
     w.sc.rc = take(M * (m / 8) > (M >> 3) * m ? M * (m / 8) : (M >> 3) * m);
+    w.sc.hp = take(hp_floats(m, M));
     w.x0 = take(M * h->ctraj);
     w.cond_keep = take(16);
     w.splitk = take(kSplitKFloats);
@@ -584,7 +586,7 @@ static TWs carve_t(const rohm_trajnet* h, int B, int T, float* base) {
         for (int i = 0; i < 4; ++i) w.ctrl_b[i] = take((M >> i) * (i == 0 ? 32 : ch[i - 1]));
         w.ctrl_mid_b = take(M16 * m);
         const size_t blk = M * (m / 8) > (M >> 3) * m ? M * (m / 8) : (M >> 3) * m;
-        w.sc_ctl.ya = take(2 * blk); w.sc_ctl.hb = take(blk); w.sc_ctl.rc = take(blk);
+        w.sc_ctl.ya = take(2 * blk); w.sc_ctl.hb = take(blk); w.sc_ctl.rc = take(blk); w.sc_ctl.hp = take(hp_floats(m, M));
         w.splitk_ctl = take(kSplitKFloats);
         w.splitk_res_ctl = take(kSplitKFloats);
     }
@@ -616,8 +618,17 @@ static int run_cond_encoder(const rohm_trajnet* h, const TWs& w, int B, int T, h
                             w.sc, s)))
             return rc;
         if (i < 3) {
-            if ((rc = down(h, h->cond_down[i], dst, 2 * ch[i], B, Ti, w.cdn[i], ch[i], s))) return rc;
-            x = w.cdn[i]; ldx = ch[i];
+            const float* src = dst;
+            int ldsrc = 2 * ch[i];
+            if (pad64(ch[i]) != ch[i]) {
+                // h_cond is the right half of a 2 ch[i]-wide row and narrower than the down conv's K chunk (32 channels at mid_dim 256): read
+                // in place, every row load would run into the next row's left half.  The conv reads a copy in hp's zero-padded rows.
+                ROHM_HIP_CHECK(hipMemcpy2DAsync(w.sc.hp, (size_t)pad64(ch[i]) * sizeof(float), dst, (size_t)2 * ch[i] * sizeof(float),
+                                                (size_t)ch[i] * sizeof(float), (size_t)B * Ti, hipMemcpyDeviceToDevice, s));
+                src = w.sc.hp; ldsrc = pad64(ch[i]);
+            }
+            if ((rc = down(h, h->cond_down[i], src, ldsrc, B, Ti, w.cdn[i], pad64(ch[i]), s))) return rc;
+            x = w.cdn[i]; ldx = pad64(ch[i]);
         }
     }
     return ROHM_OK;
@@ -691,7 +702,7 @@ static int run_denoiser(const rohm_trajnet* h, const TWs& w, int B, int T, int l
         const int Ti = T >> i, Tq = Ti / 2;
         if ((rc = upsample(h, h->up[i], x, ldx, B, Tq, w.dcat[i], 2 * ch[i], s))) return rc;
         const int co = (i == 0) ? 32 : ch[i - 1];
-        const int ldd = (i == 0) ? kPadC : co;
+        const int ldd = pad64(co);
         if ((rc = res_block(h, h->dec[i], w.dcat[i], 2 * ch[i], B, Ti, tb, ldtb, h->control ? ctrl[i] : nullptr, co,
                             w.d[i], ldd, nullptr, 0, w.sc, s)))
             return rc;
@@ -749,6 +760,13 @@ static int zero_pads(const rohm_trajnet* h, const TWs& w, size_t M, hipStream_t 
     ROHM_HIP_CHECK(hipMemsetAsync(w.d[0], 0, M * kPadC * sizeof(float), s));
     ROHM_HIP_CHECK(hipMemsetAsync(w.fin, 0, M * kPadC * sizeof(float), s));
     if (h->control) ROHM_HIP_CHECK(hipMemsetAsync(w.cz, 0, M * kPadC * sizeof(float), s));
+    const int c0 = h->mid / 8;
+    if (pad64(c0) != c0) {      // level-0 width no multiple of 64 (mid_dim 256: 32 channels): cond_down[0]'s and dec[1]'s outputs are padded too
+        ROHM_HIP_CHECK(hipMemsetAsync(w.cdn[0], 0, (M / 2) * pad64(c0) * sizeof(float), s));
+        ROHM_HIP_CHECK(hipMemsetAsync(w.d[1], 0, (M / 2) * pad64(c0) * sizeof(float), s));
+    }
+    ROHM_HIP_CHECK(hipMemsetAsync(w.sc.hp, 0, hp_floats(h->mid, M) * sizeof(float), s));
+    if (h->control) ROHM_HIP_CHECK(hipMemsetAsync(w.sc_ctl.hp, 0, hp_floats(h->mid, M) * sizeof(float), s));
     return ROHM_OK;
 }
 
@@ -831,11 +849,10 @@ int rohm_trajnet_create(rohm_trajnet_t** out, const rohm_trajnet_weights* wts, i
         if (hipMemcpy(d, src, n * sizeof(float), hipMemcpyDefault) != hipSuccess) { ok = false; err = "hipMemcpy failed"; }
         return d;
     };
-    auto pad32 = [](int c) { return (c + 63) / 64 * 64; };   // GEMM K chunks are 64 wide
     // conv: weight [cout, cin, k] (or [cin, cout, k] when transposed) + bias [cout]
     auto load_conv = [&](ConvW& c, int cout, int cin, int k, int tap0, int tap_step, int ntap, bool transposed,
                          const float* wsrc, const float* bsrc) {
-        c.cout = cout; c.cin = cin; c.cin_pad = pad32(cin); c.taps = (k == 1) ? 0 : ntap;
+        c.cout = cout; c.cin = cin; c.cin_pad = pad64(cin); c.taps = (k == 1) ? 0 : ntap;      // (GEMM K chunks are 64 wide)
         const int K = ntap * c.cin_pad;
         c.w = arena_take((size_t)cout * K);
         c.b = arena_take(cout);

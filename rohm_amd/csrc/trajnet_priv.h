@@ -61,7 +61,18 @@ __device__ __forceinline__ float mishf(float x) {
 
 constexpr int kTbSteps = 128;             // loop steps whose time path is evaluated by one launch
 
-struct Scratch { float *ya, *hb, *rc; };   // conv output, block-0 activation, 1x1 residual
+// conv output, block-0 activation, 1x1 residual; hp: the block-0 activation of a block whose channel count is no multiple of the
+// 64-wide K chunk (32 channels: dec[0], level 0 at mid_dim 256) in rows as wide as the second conv reads them (its cin_pad), the pad
+// columns cleared once per call (zero_pads) and never written
+struct Scratch { float *ya, *hb, *rc, *hp; };
+inline int pad64(int c) { return (c + 63) / 64 * 64; }      // row width of an activation that feeds a GEMM: whole 64-wide K chunks
+// row width and buffer of a residual block's block-0 activation: the second conv reads cin_pad floats of every row
+inline int hb_ld(const ResW& r) { return r.b1.conv.cin_pad > r.cout ? r.b1.conv.cin_pad : r.cout; }
+inline float* hb_buf(const ResW& r, const Scratch& sc) { return r.b1.conv.cin_pad > r.cout ? sc.hp : sc.hb; }
+// floats of hp.  Its users: dec[0] (32 channels, M rows of 64 floats) at every width; where the level-0 width c0 = mid / 8 is no multiple
+// of 64 (mid_dim 256: 32) also the blocks of width c0 (M rows of pad64(c0) floats at level 0, M / 2 rows in dec[1]).  The widths of
+// the deeper levels, c0 << i with i >= 1, are multiples of 64 and keep hb.
+inline size_t hp_floats(int mid, size_t M) { const int c0 = mid / 8; return M * (size_t)(pad64(c0) != c0 ? pad64(c0) : kPadC); }
 
 // ---- workspace ---------------------------------------------------------------------------------------------
 struct TWs {

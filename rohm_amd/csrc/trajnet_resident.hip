@@ -656,19 +656,21 @@ struct Builder {
                 break;
             }
         }
-        if (o.q < 1 || c.cout % 16 != 0 || c.cin_pad % kKC != 0 || ((n + o.q - 1) / o.q) * o.rsplit * (c.cout / 16) > kMaxItems) ok = false;
+        if (o.q < 1 || c.cout % 16 != 0 || c.cin_pad % kKC != 0 || lda < c.cin_pad ||      // (a row load takes cin_pad floats)
+             ((n + o.q - 1) / o.q) * o.rsplit * (c.cout / 16) > kMaxItems) ok = false;
         return o;
     }
     // ResidualTemporalBlock (heads.py:43-54) as two layers
     void res_block(const ResW& r, const float* x, int ldx, int Tl, const float* add2, int ldadd2, float* dst, int lddst, float* dst2, int lddst2,
                    const Scratch& sc, std::vector<ROp>& out) {
         static const int offs5[5] = {-2, -1, 0, 1, 2};
-        const int co = r.cout;
-        ROp a = conv(r.b0.conv, x, ldx, Tl, Tl, 1, 5, offs5, sc.hb, co, Tl);
+        const int co = r.cout, ldh = hb_ld(r);
+        float* const hb = hb_buf(r, sc);
+        ROp a = conv(r.b0.conv, x, ldx, Tl, Tl, 1, 5, offs5, hb, ldh, Tl);
         a.gn = co / 8; a.gamma = r.b0.g; a.beta = r.b0.be; a.tb_off = r.tb_off;
         if (r.has_res) { a.Wres = r.res.w; a.bres = r.res.b; a.res_out = sc.rc; a.ld_res_out = co; }
         out.push_back(a);
-        ROp b = conv(r.b1.conv, sc.hb, co, Tl, Tl, 1, 5, offs5, dst, lddst, Tl);
+        ROp b = conv(r.b1.conv, hb, ldh, Tl, Tl, 1, 5, offs5, dst, lddst, Tl);
         b.gn = co / 8; b.gamma = r.b1.g; b.beta = r.b1.be;
         if (r.has_res) { b.res = sc.rc; b.ldres = co; } else { b.res = x; b.ldres = ldx; }
         b.add2 = add2; b.ldadd2 = ldadd2; b.dst2 = dst2; b.lddst2 = lddst2;
@@ -712,7 +714,7 @@ struct Builder {
             const int Ti = T >> i;
             up(h->up[i], x, ldx, Ti / 2, w.dcat[i], 2 * ch[i], U);
             const int co = (i == 0) ? 32 : ch[i - 1];
-            const int ldd = (i == 0) ? kPadC : co;
+            const int ldd = pad64(co);
             res_block(h->dec[i], w.dcat[i], 2 * ch[i], Ti, h->control ? w.ctrl[i] : nullptr, co, w.d[i], ldd, nullptr, 0, w.sc, U);
             x = w.d[i]; ldx = ldd;
         }
