@@ -936,6 +936,30 @@ int rohm_export_smplx(const rohm_smplx_t* h, const float* repr, long long in_str
                       const double* rigid, const int* frame_clip, const int* frame_t, int C, int T, int N,
                       double* params, float* contact, rohm_stream_t stream);
 
+/* rohm_export_smplx with a cross-fade over the frames two clips share (csrc/export.hip), one launch for all N frames.
+ * Every clip is denoised on its own, so at a window boundary the plain gather jumps in position, heading and pose; here
+ * output frame n has candidate a = (frame_clip[n], frame_t[n]) and, where frame_clip_b[n] >= 0, candidate b =
+ * (frame_clip_b[n], frame_t_b[n]) (device int32 [N]) with the weight alpha[n] of b (device float64 [N];
+ * rohm_amd.export.plan_blend makes the five arrays: a linear ramp strictly inside (0, 1) over the shared frames).  repr,
+ * strides, mean294 / std294, transf, rigid, C, T as in rohm_export_smplx.  Both candidates go through exactly the arithmetic
+ * of rohm_export_smplx (its device functions), each with its own clip's transf and its own betas' pelvis offset.
+ * One candidate (frame_clip_b[n] < 0), or alpha[n] == 0: the row is candidate a's bits, what rohm_export_smplx writes for
+ * (frame_clip[n], frame_t[n]).  Otherwise, in float64: the 22 rotations are the shortest-arc quaternion slerp of the two
+ * candidates' final rotation vectors by the rule of rohm_track_resample (lerp weights when sin(omega) < 1e-8, |rotation
+ * vector| <= pi through the atan2 angle); transl, betas and the four contact channels are a + alpha (b - a), contact
+ * rounded to float32 once.
+ * params [N,79] float64 (the smplx_world layout); contact [N,4] float32 (may be NULL); disagree [N,23] float64 (may be
+ * NULL): what the two candidates disagreed by -- columns 0..21 the geodesic angle (rad) between their rotations per joint,
+ * column 22 the distance (m) between their pelvis positions transl + d(betas) -- whatever alpha is, and zero where there
+ * is one candidate.  An index pair outside [0, C) x [0, T) on the a side, or on the b side when frame_clip_b[n] >= 0, gives
+ * a NaN row in all three outputs, never a read outside the arrays.  Every output element is written.  No atomics: the
+ * same input gives the same bits.  N == 0 returns without a launch. */
+int rohm_export_smplx_blend(const rohm_smplx_t* h, const float* repr, long long in_stride_b, long long in_stride_t,
+                            long long in_stride_c, const float* mean294, const float* std294, const float* transf,
+                            const double* rigid, const int* frame_clip, const int* frame_t, const int* frame_clip_b,
+                            const int* frame_t_b, const double* alpha, int C, int T, int N, double* params, float* contact,
+                            double* disagree, rohm_stream_t stream);
+
 /* A track of per-frame SMPL-X estimates at any frame rate, with frames that have no fit, resampled to the times
  * times_dst [n_out] (the 30 fps grid of the networks, or a reconstruction back onto the source's time stamps).  No
  * counterpart in the reference.  All arrays are device memory: times_src [N] float64 seconds, strictly increasing;

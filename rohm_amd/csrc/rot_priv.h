@@ -75,6 +75,58 @@ __device__ __forceinline__ void euler_zxy_deg_to_rotvec_f64(const double* e, dou
     rv[0] = sc2 * q[0]; rv[1] = sc2 * q[1]; rv[2] = sc2 * q[2];
 }
 
+// scipy's Rotation.from_rotvec: (x, y, z, w), incl. the small-angle series (cf. rotvec_to_matrix_f64)
+__device__ __forceinline__ void rotvec_to_quat_f64(const double* rv, double* q) {
+    const double a2 = rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2];
+    const double a = sqrt(a2);
+    const double sc = (a <= 1e-3) ? 0.5 - a2 / 48.0 + a2 * a2 / 3840.0 : sin(a / 2.0) / a;
+    q[0] = sc * rv[0]; q[1] = sc * rv[1]; q[2] = sc * rv[2]; q[3] = cos(a / 2.0);
+}
+
+// unit quaternion -> shortest rotation vector (the tail of matrix_to_rotvec_f64)
+__device__ __forceinline__ void quat_to_rotvec_f64(double* q, double* rv) {
+    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int i = 0; i < 4; ++i) q[i] /= n;
+    if (q[3] < 0) for (int i = 0; i < 4; ++i) q[i] = -q[i];
+    const double ang = 2 * atan2(sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]), q[3]);
+    const double a2 = ang * ang;
+    const double sc = (ang <= 1e-3) ? 2 + a2 / 12 + 7 * a2 * a2 / 2880 : ang / sin(ang / 2);
+    rv[0] = sc * q[0]; rv[1] = sc * q[1]; rv[2] = sc * q[2];
+}
+
+__device__ __forceinline__ void slerp_rotvec_f64(const double* r0, const double* r1, double alpha, double* out) {
+    double q0[4], q1[4], q[4];
+    rotvec_to_quat_f64(r0, q0);
+    rotvec_to_quat_f64(r1, q1);
+    double d = q0[0] * q1[0] + q0[1] * q1[1] + q0[2] * q1[2] + q0[3] * q1[3];
+    if (d < 0) {
+        d = -d;
+        for (int i = 0; i < 4; ++i) q1[i] = -q1[i];
+    }
+    const double omega = atan2(sqrt(fmax(1.0 - d * d, 0.0)), d);
+    const double so = sin(omega);
+    double w0 = 1.0 - alpha, w1 = alpha;
+    if (!(so < 1e-8)) {
+        w0 = sin((1.0 - alpha) * omega) / so;
+        w1 = sin(alpha * omega) / so;
+    }
+    for (int i = 0; i < 4; ++i) q[i] = w0 * q0[i] + w1 * q1[i];
+    quat_to_rotvec_f64(q, out);
+}
+
+// angle (rad) of the relative rotation between two rotation vectors: 2 atan2(|v|, |w|) of qa^-1 qb, accurate at angle 0
+// (an arccos of the trace is not); tests/track_ref.py `geodesic`
+__device__ __forceinline__ double geodesic_rotvec_f64(const double* ra, const double* rb) {
+    double qa[4], qb[4];
+    rotvec_to_quat_f64(ra, qa);
+    rotvec_to_quat_f64(rb, qb);
+    const double w = qa[3] * qb[3] + qa[0] * qb[0] + qa[1] * qb[1] + qa[2] * qb[2];
+    const double v[3] = {qa[3] * qb[0] - qb[3] * qa[0] - (qa[1] * qb[2] - qa[2] * qb[1]),
+                         qa[3] * qb[1] - qb[3] * qa[1] - (qa[2] * qb[0] - qa[0] * qb[2]),
+                         qa[3] * qb[2] - qb[3] * qa[2] - (qa[0] * qb[1] - qa[1] * qb[0])};
+    return 2.0 * atan2(sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), fabs(w));
+}
+
 __device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
 __device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
 __device__ __forceinline__ float sub(float a, float b) { return __fsub_rn(a, b); }

@@ -28,45 +28,7 @@ constexpr int kTrackCols = 79;                 // global_orient 3, transl 3, bet
 constexpr int kTrackRot = 22;                  // root + 21 body joints
 constexpr int kTrackFixedSlots = kTrackRot + 1;
 
-// scipy's Rotation.from_rotvec: (x, y, z, w), incl. the small-angle series (cf. rotvec_to_matrix_f64)
-__device__ __forceinline__ void rotvec_to_quat_f64(const double* rv, double* q) {
-    const double a2 = rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2];
-    const double a = sqrt(a2);
-    const double sc = (a <= 1e-3) ? 0.5 - a2 / 48.0 + a2 * a2 / 3840.0 : sin(a / 2.0) / a;
-    q[0] = sc * rv[0]; q[1] = sc * rv[1]; q[2] = sc * rv[2]; q[3] = cos(a / 2.0);
-}
-
-// unit quaternion -> shortest rotation vector (the tail of matrix_to_rotvec_f64)
-__device__ __forceinline__ void quat_to_rotvec_f64(double* q, double* rv) {
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    for (int i = 0; i < 4; ++i) q[i] /= n;
-    if (q[3] < 0) for (int i = 0; i < 4; ++i) q[i] = -q[i];
-    const double ang = 2 * atan2(sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]), q[3]);
-    const double a2 = ang * ang;
-    const double sc = (ang <= 1e-3) ? 2 + a2 / 12 + 7 * a2 * a2 / 2880 : ang / sin(ang / 2);
-    rv[0] = sc * q[0]; rv[1] = sc * q[1]; rv[2] = sc * q[2];
-}
-
-__device__ __forceinline__ void slerp_rotvec_f64(const double* r0, const double* r1, double alpha, double* out) {
-    double q0[4], q1[4], q[4];
-    rotvec_to_quat_f64(r0, q0);
-    rotvec_to_quat_f64(r1, q1);
-    double d = q0[0] * q1[0] + q0[1] * q1[1] + q0[2] * q1[2] + q0[3] * q1[3];
-    if (d < 0) {
-        d = -d;
-        for (int i = 0; i < 4; ++i) q1[i] = -q1[i];
-    }
-    const double omega = atan2(sqrt(fmax(1.0 - d * d, 0.0)), d);
-    const double so = sin(omega);
-    double w0 = 1.0 - alpha, w1 = alpha;
-    if (!(so < 1e-8)) {
-        w0 = sin((1.0 - alpha) * omega) / so;
-        w1 = sin(alpha * omega) / so;
-    }
-    for (int i = 0; i < 4; ++i) q[i] = w0 * q0[i] + w1 * q1[i];
-    quat_to_rotvec_f64(q, out);
-}
-
+// (rotvec_to_quat_f64, quat_to_rotvec_f64 and slerp_rotvec_f64 live in rot_priv.h: export.hip blends with them too)
 struct TrackArgs {
     const double* times_src;   // [N]
     const int* valid_idx;      // [Nv] ascending, inside [0, N)

@@ -310,5 +310,10 @@ class DataloaderTrack(DataloaderVideo):
 
     def export_plan(self, keep='first', rows=None):
         """(frame_clip, frame_t, n_frames) for `export.export_params(plan=...)`, the tail clip included.  rows: rows per clip
-        of the representation to export (default clip_len; the drivers' pose stage keeps clip_len - 2)."""
+        of the representation to export (default clip_len; the drivers' pose stage keeps clip_len - 2).  keep='blend':
+        `export.plan_blend`'s (frame_clip_a, frame_t_a, frame_clip_b, frame_t_b, alpha, n_frames), for a cross-fade over the
+        frames two clips share."""
+        if keep == 'blend':
+            from ..export import plan_blend
+            return plan_blend(self.clip_starts, self.clip_len if rows is None else rows)
         return frames_plan(self.clip_starts, self.clip_len if rows is None else rows, keep)

@@ -10,8 +10,16 @@ existing skinning (`rohm_smplx_forward`) fed with the exported parameters, so th
         --recordings N0Sofa_00034_01 --dataset_root /data/PROX --body_model_path body_models/smplx_model \\
         --out exported --frame camera --formats npz,prox_fits --meshes ply --mesh_interval 30 --clip_len 145
 
-Stitching: clip c holds recording frames c * (clip_len - overlap_len) ... + T - 1 (T rows per clip); a frame two clips share
-is taken from the earlier clip (`keep='first'`) or the later one (`keep='last'`); nothing is blended.  `betas='mean'`
+Stitching: clip c holds recording frames c * (clip_len - overlap_len) ... + T - 1 (T rows per clip).  Every clip is denoised
+on its own, in its own canonical frame, from its own noise, so two clips disagree on the frames they share.  `keep='first'`
+(the default) takes such a frame from the earlier clip and `keep='last'` from the later one: a gather, and the body jumps at
+every window boundary.  `keep='blend'` cross-fades instead (`plan_blend`, `rohm_export_smplx_blend`, the same launch that
+converts the representation): over the m frames clips c - 1 and c share the weight of clip c ramps linearly as
+(i + 1) / (m + 1), i = 0 .. m - 1, strictly inside (0, 1); rotations are slerped, transl / betas / contact interpolated, and
+`ExportResult.disagree` keeps what the two clips disagreed by.  No frame takes more than two clips: a clip that would be the
+third (heavy overlaps, the track loader's tail clip) is trimmed at its beginning.  With the reference's overlap of 2 there is
+little to fade over; run the drivers with a larger `--window_size` (16 to 32 frames, about half a second to a second) when
+the export is meant to be blended.  `betas='mean'`
 replaces every frame's shape by the recording's mean shape before the kernel runs (so the pelvis offset and the translation
 are consistent with it) -- a departure from the reference, which keeps per-frame shapes.
 """
@@ -57,6 +65,43 @@ def plan_frames(n_clips, T, clip_len, overlap_len, keep='first'):
     return clip.astype(np.int32), (f - clip * stride).astype(np.int32), n_frames
 
 
+def plan_blend(starts, rows):
+    """The cross-fade plan for clips at ascending `starts` (starts[0] == 0) holding `rows` rows each ->
+    (frame_clip_a, frame_t_a, frame_clip_b, frame_t_b int32 [n], alpha float64 [n], n_frames), n_frames = starts[-1] + rows.
+
+    With hi_c = starts[c] + rows the active range of clip c is [lo_c, hi_c): lo_0 = 0, lo_1 = starts[1] and
+    lo_c = max(starts[c], hi_{c-2}) for c >= 2, so no frame is in the active range of more than two clips (a clip that would
+    be the third is trimmed at its beginning: its own edge rows).  A frame f in [lo_c, hi_{c-1}) is shared by a = c - 1 and
+    b = c with alpha = (i + 1) / (m + 1), m = hi_{c-1} - lo_c, i = f - lo_c: the weight of b, a linear ramp strictly inside
+    (0, 1).  Every other frame belongs to one clip: frame_clip_b = -1, frame_t_b = 0, alpha = 0.  Rows are f - starts[clip].
+    Regular windows: starts = arange(C) * (clip_len - overlap_len)."""
+    s = np.asarray(starts, dtype=np.int64).reshape(-1)
+    rows = int(rows)
+    if s.size == 0:
+        z = np.zeros(0, np.int32)
+        return z, z.copy(), z.copy(), z.copy(), np.zeros(0, np.float64), 0
+    if rows < 1 or s[0] != 0 or (np.diff(s) <= 0).any():
+        raise ValueError('plan_blend needs rows >= 1 and ascending starts from 0')
+    hi = s + rows
+    if (s[1:] > hi[:-1]).any():
+        raise ValueError(f'clips of {rows} rows at starts {s.tolist()} leave frames uncovered')
+    lo = s.copy()
+    lo[2:] = np.maximum(s[2:], hi[:-2])
+    n_frames = int(hi[-1])
+    clip_a, clip_b = np.zeros(n_frames, np.int64), np.full(n_frames, -1, np.int64)
+    alpha = np.zeros(n_frames, np.float64)
+    for c in range(1, len(s)):
+        clip_a[hi[c - 1]:hi[c]] = c                                  # until clip c + 1 takes over, clip c alone
+        m = int(hi[c - 1] - lo[c])
+        if m > 0:
+            clip_b[lo[c]:hi[c - 1]] = c
+            alpha[lo[c]:hi[c - 1]] = (np.arange(m, dtype=np.float64) + 1.0) / (m + 1.0)
+    f = np.arange(n_frames, dtype=np.int64)
+    t_a = f - s[clip_a]
+    t_b = np.where(clip_b >= 0, f - s[np.maximum(clip_b, 0)], 0)
+    return clip_a.astype(np.int32), t_a.astype(np.int32), clip_b.astype(np.int32), t_b.astype(np.int32), alpha, n_frames
+
+
 def first_pass_rows(trans_scene2cano):
     """Rows of a drivers' pickle that belong to the first pass over the recording.  The drivers' batch loop restarts its
     loader when it runs out (`drivers.results.step_schedule`): a clip count that is a multiple of the batch size gets its first
@@ -71,12 +116,17 @@ def first_pass_rows(trans_scene2cano):
 # ---- the export ----------------------------------------------------------------------------------------------------------
 class ExportResult:
     """Device tensors of an exported track: params79 [N, 79] float64 (global_orient 3, transl 3, betas 10, body_pose 63) and its
-    four views, joints [N, 22, 3] float32, contact [N, 4] float32, frame_clip / frame_t int32 [N], coordinate_frame."""
+    four views, joints [N, 22, 3] float32, contact [N, 4] float32, frame_clip / frame_t int32 [N], coordinate_frame.
+    A blended export (keep='blend') also has frame_clip_b / frame_t_b int32 [N] (-1 / 0 where one clip gave the frame), alpha
+    float64 [N] (the weight of clip b) and disagree [N, 23] float64: the geodesic angle (rad) between the two clips' rotations
+    per joint and, in column 22, the distance (m) between their pelvis positions; they are None otherwise."""
 
-    def __init__(self, params79, joints, contact, frame_clip, frame_t, coordinate_frame, times=None, gap=None):
+    def __init__(self, params79, joints, contact, frame_clip, frame_t, coordinate_frame, times=None, gap=None, frame_clip_b=None,
+                 frame_t_b=None, alpha=None, disagree=None):
         self.params79, self.joints, self.contact = params79, joints, contact
         self.frame_clip, self.frame_t, self.coordinate_frame = frame_clip, frame_t, coordinate_frame
         self.times, self.gap = times, gap          # tracks: seconds [N] float64 and "no evidence here" [N] uint8 (host arrays)
+        self.frame_clip_b, self.frame_t_b, self.alpha, self.disagree = frame_clip_b, frame_t_b, alpha, disagree
         for k, (a, b) in PARAM_COLS.items():
             setattr(self, k, params79[:, a:b])
 
@@ -120,7 +170,13 @@ def export_params(repr, transf, body_model, clip_len=None, overlap_len=2, frame=
     when it is still normalised.  transf [C, 4, 4]: scene -> canonical (`trans_scene2cano_list`, `transf_matrix`), None for
     clips that stay in their canonical frame.  frame='camera' applies inv(cam2world) after the way back to the scene.
     clip_len defaults to T + 1 (the loaders' clips); `plan` = (frame_clip, frame_t) overrides `plan_frames`.
-    betas='mean' exports the recording's mean shape for every frame (not what the reference does: it keeps per-frame shapes)."""
+    keep='blend' cross-fades the frames two clips share (`plan_blend`, one launch of `rohm_export_smplx_blend`); `plan` may
+    then be the 5 arrays of a blend plan (frame_clip_a, frame_t_a, frame_clip_b, frame_t_b, alpha), and a plan of 5 arrays
+    blends whatever `keep` says.  keep='first' / 'last' run `rohm_export_smplx` as before.
+    betas='mean' exports the recording's mean shape for every frame (not what the reference does: it keeps per-frame shapes);
+    in a blended export the mean is taken over the candidate-a rows."""
+    if keep not in ('first', 'last', 'blend'):
+        raise ValueError(f"keep must be 'first', 'last' or 'blend', got {keep!r}")
     if frame not in ('scene', 'camera'):
         raise ValueError(f"frame must be 'scene' or 'camera', got {frame!r}")
     if betas not in ('frame', 'mean'):
@@ -139,11 +195,22 @@ def export_params(repr, transf, body_model, clip_len=None, overlap_len=2, frame=
     if frame == 'camera':
         inv = np.linalg.inv(np.asarray(cam2world.detach().cpu() if torch.is_tensor(cam2world) else cam2world, dtype=np.float64))
         rigid = torch.from_numpy(np.ascontiguousarray(inv.reshape(4, 4))).to(device)
-    if plan is None:
+    if plan is None and keep == 'blend':
+        stride = (T + 1 if clip_len is None else int(clip_len)) - int(overlap_len)
+        if stride < 1:
+            raise ValueError(f'need clip_len > overlap_len (got {clip_len}, {overlap_len})')
+        plan = plan_blend(np.arange(C, dtype=np.int64) * stride, T)[:5]
+    elif plan is None:
         plan = plan_frames(C, T, T + 1 if clip_len is None else clip_len, overlap_len, keep)[:2]
-    fc = torch.as_tensor(np.asarray(plan[0], dtype=np.int32)).to(device) if not torch.is_tensor(plan[0]) else plan[0].to(device, torch.int32)
-    ft = torch.as_tensor(np.asarray(plan[1], dtype=np.int32)).to(device) if not torch.is_tensor(plan[1]) else plan[1].to(device, torch.int32)
-    fc, ft = fc.contiguous(), ft.contiguous()
+    plan = tuple(plan)
+    blend = len(plan) >= 5
+    if keep == 'blend' and not blend:
+        raise ValueError("keep='blend' needs the 5 arrays of `plan_blend` as plan, got %d" % len(plan))
+
+    def index(a, dtype, np_dtype):
+        a = a.to(device, dtype) if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, dtype=np_dtype)).to(device)
+        return a.contiguous()
+    fc, ft = index(plan[0], torch.int32, np.int32), index(plan[1], torch.int32, np.int32)
     mean = std = None
     if stats is not None:
         from .data_loaders.motion_representation import _stats
@@ -159,8 +226,14 @@ def export_params(repr, transf, body_model, clip_len=None, overlap_len=2, frame=
         ok = (fc >= 0) & (fc < C) & (ft >= 0) & (ft < T)
         rows = x[fc[ok].long(), ft[ok].long(), 280:290]
         x[:, :, 280:290] = rows.double().mean(dim=0).float()
-    params, contact = ops.export_smplx(nat.handle, x, layout, fc, ft, transf=tf, rigid=rigid, mean=mean, std=std)
-    res = ExportResult(params, None, contact, fc, ft, frame)
+    if blend:
+        fcb, ftb, al = index(plan[2], torch.int32, np.int32), index(plan[3], torch.int32, np.int32), index(plan[4], torch.float64, np.float64)
+        params, contact, disagree = ops.export_smplx_blend(nat.handle, x, layout, fc, ft, fcb, ftb, al, transf=tf, rigid=rigid, mean=mean,
+                                                           std=std)
+        res = ExportResult(params, None, contact, fc, ft, frame, frame_clip_b=fcb, frame_t_b=ftb, alpha=al, disagree=disagree)
+    else:
+        params, contact = ops.export_smplx(nat.handle, x, layout, fc, ft, transf=tf, rigid=rigid, mean=mean, std=std)
+        res = ExportResult(params, None, contact, fc, ft, frame)
     res.joints = _joints(nat, res.pose_f32(), res.betas.float().contiguous(), res.transl.float().contiguous())
     return res
 
@@ -172,7 +245,8 @@ def resample_params(result, times_from, times_to, body_model=None, gap_from=None
     times_from is that row's bits; contact, frame_clip and frame_t are those of the row at the left bracket.  With `body_model`
     the joints are recomputed from the new parameters (`rohm_smplx_joints`).  The result carries `times` = times_to and `gap`
     [n] uint8: 1 where times_to lies outside times_from (the nearest row is held), where the brackets are further apart
-    than max_gap (default 1.5 intervals of times_from) or where `gap_from` [N] is set at the left bracket."""
+    than max_gap (default 1.5 intervals of times_from) or where `gap_from` [N] is set at the left bracket.  A blended
+    export's frame_clip_b, frame_t_b, alpha and disagree are those of the row at the left bracket too."""
     from .data_loaders.track import resample_track
     tf = np.asarray(times_from, dtype=np.float64).reshape(-1)
     tt = np.asarray(times_to, dtype=np.float64).reshape(-1)
@@ -187,6 +261,9 @@ def resample_params(result, times_from, times_to, body_model=None, gap_from=None
     res = ExportResult(out['params'], None, result.contact[left] if result.contact is not None else None, result.frame_clip[left],
                        result.frame_t[left], result.coordinate_frame, times=tt, gap=gap)
     res.src_index = out['src_index']
+    if result.disagree is not None:
+        res.frame_clip_b, res.frame_t_b, res.alpha, res.disagree = (getattr(result, k)[left] for k in ('frame_clip_b', 'frame_t_b', 'alpha',
+                                                                                                      'disagree'))
     if body_model is not None:
         nat = native_for(body_model, device)
         res.joints = _joints(nat, res.pose_f32(), res.betas.float().contiguous(), res.transl.float().contiguous())
@@ -214,6 +291,17 @@ def export_vertices(result, body_model, every=1, chunk=256):
     return torch.cat(parts, dim=0)
 
 
+def seam_summary(result):
+    """(number of seams, largest seam_angle in rad, largest seam_dist in m) of a blended export; a seam is a pair of clips
+    that share frames."""
+    b = _host(result.frame_clip_b).reshape(-1)
+    if not (b >= 0).any():
+        return 0, 0.0, 0.0
+    pairs = np.stack([_host(result.frame_clip).reshape(-1)[b >= 0], b[b >= 0]], axis=1)
+    dis = _host(result.disagree).reshape(-1, 23)[b >= 0]
+    return len(np.unique(pairs, axis=0)), float(dis[:, :22].max()), float(dis[:, 22].max())
+
+
 # ---- writers (host) ----------------------------------------------------------------------------------------------------------
 def _host(t, dtype=None):
     a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
@@ -229,7 +317,9 @@ def _names(frame_names, n):
 
 def write_npz(path, result, frame_names):
     """One smplx_params.npz per recording: global_orient / transl / betas / body_pose (float32), joints, foot_contact,
-    frame_names, frame_clip, coordinate_frame, gender; for a track also times (seconds) and gap (1 = no evidence at this frame)."""
+    frame_names, frame_clip, coordinate_frame, gender; for a track also times (seconds) and gap (1 = no evidence at this frame);
+    for a blended export also frame_clip_b (-1: one clip), blend_alpha, seam_angle (rad: the largest of the 22 joints' geodesic
+    angles between the two clips) and seam_dist (m, between their pelvis positions)."""
     p = _host(result.params79)
     d = os.path.dirname(path)
     if d:
@@ -239,6 +329,10 @@ def write_npz(path, result, frame_names):
         out['times'] = np.asarray(result.times, dtype=np.float64)
     if getattr(result, 'gap', None) is not None:
         out['gap'] = np.asarray(result.gap, dtype=np.uint8)
+    if getattr(result, 'disagree', None) is not None:
+        dis = _host(result.disagree, np.float64).reshape(len(p), 23)
+        out.update(frame_clip_b=_host(result.frame_clip_b, np.int32), blend_alpha=_host(result.alpha, np.float64),
+                   seam_angle=dis[:, :22].max(axis=1) if len(p) else np.zeros(0), seam_dist=dis[:, 22])
     np.savez(path, joints=_host(result.joints, np.float32), foot_contact=_host(result.contact, np.float32),
              frame_names=np.array(_names(frame_names, len(p))), frame_clip=_host(result.frame_clip, np.int32),
              coordinate_frame=np.str_(result.coordinate_frame), gender=np.str_('neutral'), **out)
@@ -320,7 +414,8 @@ def build_parser():
     ap.add_argument('--formats', type=str, default='npz', help='comma-separated: npz, prox_fits')
     ap.add_argument('--meshes', choices=['none', 'ply', 'obj'], default='none')
     ap.add_argument('--mesh_interval', type=int, default=1)
-    ap.add_argument('--keep', choices=['first', 'last'], default='first')
+    ap.add_argument('--keep', choices=['first', 'last', 'blend'], default='first',
+                    help='a frame two clips share: from the earlier clip, from the later one, or a cross-fade of both')
     ap.add_argument('--betas', choices=['frame', 'mean'], default='frame')
     ap.add_argument('--overlap_len', type=int, default=2)
     ap.add_argument('--clip_len', type=int, default=0, help='frames per loader clip; 0 = rows per clip + 1.  The drivers\' pose '
@@ -412,9 +507,14 @@ def _export_track(args, data, rec, transf, recording, body, device):
     if missing:
         raise SystemExit(f'--dataset track: the pickle has no {missing}; it was not written by `python -m rohm_amd.drivers track`')
     starts = np.asarray(data['clip_starts']).reshape(-1)[:len(rec)]
-    fc, ft, n = frames_plan(starts, rec.shape[1], args.keep)
+    if args.keep == 'blend':
+        plan = plan_blend(starts, rec.shape[1])
+        plan, n = plan[:5], plan[5]
+    else:
+        fc, ft, n = frames_plan(starts, rec.shape[1], args.keep)
+        plan = (fc, ft)
     res = export_params(rec[:len(starts)], transf[:len(starts)], body, frame=args.frame, cam2world=np.asarray(data['cam2world']),
-                        betas=args.betas, plan=(fc, ft), device=device)
+                        betas=args.betas, keep=args.keep, plan=plan, device=device)
     times30, gap30 = np.asarray(data['times_dst'], dtype=np.float64)[:n], np.asarray(data['gap'], dtype=np.uint8)[:n]
     src_names = [str(s) for s in data['source_frame_names']]
     if args.times == '30fps':
@@ -442,6 +542,9 @@ def _write(args, out, recording, res, body, names, info):
     if args.meshes != 'none':
         n_mesh = write_meshes(out, res, body, names, args.mesh_interval, args.meshes)
     print(f'[rohm_amd.export] {recording}: {len(res)} frames ({res.coordinate_frame}), {n_mesh} meshes -> {out}')
+    if res.disagree is not None:
+        n_seams, angle, dist = seam_summary(res)
+        print(f'[rohm_amd.export] {recording}: {n_seams} seams blended, largest seam_angle {angle:.4f} rad, largest seam_dist {dist:.4f} m')
     return len(res)
 
 

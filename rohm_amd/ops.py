@@ -184,18 +184,10 @@ def ddpm_step_table(x_t, x0, noise, tables, t, grad_a=None, w_a=0.0, grad_b=None
     return out
 
 
-def export_smplx(handle, repr_full, layout, frame_clip, frame_t, transf=None, rigid=None, mean=None, std=None, want_contact=True):
-    """rohm_export_smplx (include/rohm_hip.h): rows of the 294-channel representation -> (params [N, 79] float64 in the
-    smplx_world layout global_orient 3, transl 3, betas 10, body_pose 63; contact [N, 4] float32 or None).
-
-    `handle`: the body model's native handle (body_model.native_for(...).handle).  `repr_full`: float32 [C, T, 294]
-    (layout 'btc') or [C, 294, 1, T] ('bc1t'), read in place through its strides.  `frame_clip` / `frame_t`: int32 [N]
-    device tensors, the clip and row every output frame is gathered from (out of range -> a NaN row).  `transf` [C, 4, 4]
-    float32 (scene -> canonical, inverted on the device), `rigid` [4, 4] float64 (applied after the inverse), `mean` / `std`
-    float32 [294] (both or neither) may be None."""
-    _lib.require_hip(repr_full, frame_clip, frame_t, transf, rigid, mean, std)
+def _export_args(name, repr_full, layout, frame_clip, frame_t, transf, rigid, mean, std):
+    """The checks `export_smplx` and `export_smplx_blend` share -> (C, T, stride_b, stride_t, stride_c)."""
     if repr_full.dtype != torch.float32:
-        raise TypeError('export_smplx reads a float32 representation')
+        raise TypeError(f'{name} reads a float32 representation')
     if layout == 'btc' and repr_full.dim() == 3 and repr_full.shape[2] == 294:
         n_clip, T, sb, st, sc = repr_full.shape[0], repr_full.shape[1], repr_full.stride(0), repr_full.stride(1), repr_full.stride(2)
     elif layout == 'bc1t' and repr_full.dim() == 4 and repr_full.shape[1] == 294 and repr_full.shape[2] == 1:
@@ -206,10 +198,24 @@ def export_smplx(handle, repr_full, layout, frame_clip, frame_t, transf=None, ri
         raise ValueError('frame_clip and frame_t must be int32 [N]')
     if (mean is None) != (std is None):
         raise ValueError('pass both mean and std or neither')
-    for name, t, shape, dt in (('transf', transf, (n_clip, 4, 4), torch.float32), ('rigid', rigid, (4, 4), torch.float64),
+    for what, t, shape, dt in (('transf', transf, (n_clip, 4, 4), torch.float32), ('rigid', rigid, (4, 4), torch.float64),
                                ('mean', mean, (294,), torch.float32), ('std', std, (294,), torch.float32)):
         if t is not None and (tuple(t.shape) != shape or t.dtype != dt):
-            raise ValueError(f'{name} must be {dt} {list(shape)}, got {t.dtype} {list(t.shape)}')
+            raise ValueError(f'{what} must be {dt} {list(shape)}, got {t.dtype} {list(t.shape)}')
+    return n_clip, T, sb, st, sc
+
+
+def export_smplx(handle, repr_full, layout, frame_clip, frame_t, transf=None, rigid=None, mean=None, std=None, want_contact=True):
+    """rohm_export_smplx (include/rohm_hip.h): rows of the 294-channel representation -> (params [N, 79] float64 in the
+    smplx_world layout global_orient 3, transl 3, betas 10, body_pose 63; contact [N, 4] float32 or None).
+
+    `handle`: the body model's native handle (body_model.native_for(...).handle).  `repr_full`: float32 [C, T, 294]
+    (layout 'btc') or [C, 294, 1, T] ('bc1t'), read in place through its strides.  `frame_clip` / `frame_t`: int32 [N]
+    device tensors, the clip and row every output frame is gathered from (out of range -> a NaN row).  `transf` [C, 4, 4]
+    float32 (scene -> canonical, inverted on the device), `rigid` [4, 4] float64 (applied after the inverse), `mean` / `std`
+    float32 [294] (both or neither) may be None."""
+    _lib.require_hip(repr_full, frame_clip, frame_t, transf, rigid, mean, std)
+    n_clip, T, sb, st, sc = _export_args('export_smplx', repr_full, layout, frame_clip, frame_t, transf, rigid, mean, std)
     N, dev = frame_clip.numel(), repr_full.device
     params = torch.empty(N, 79, device=dev, dtype=torch.float64)
     contact = torch.empty(N, 4, device=dev, dtype=torch.float32) if want_contact else None
@@ -217,3 +223,31 @@ def export_smplx(handle, repr_full, layout, frame_clip, frame_t, transf=None, ri
                                   ptr(frame_clip), ptr(frame_t), n_clip, T, N, ptr(params), ptr(contact), stream_ptr(dev)),
           'rohm_export_smplx')
     return params, contact
+
+
+def export_smplx_blend(handle, repr_full, layout, frame_clip, frame_t, frame_clip_b, frame_t_b, alpha, transf=None, rigid=None,
+                       mean=None, std=None, want_contact=True, want_disagree=True):
+    """rohm_export_smplx_blend (include/rohm_hip.h): `export_smplx` with a cross-fade over the frames two clips share ->
+    (params [N, 79] float64, contact [N, 4] float32 or None, disagree [N, 23] float64 or None).
+
+    Candidate a of frame n is (frame_clip[n], frame_t[n]); where frame_clip_b[n] >= 0, candidate b is (frame_clip_b[n],
+    frame_t_b[n]) with weight alpha[n] (int32 / int32 / float64 [N] device tensors; `rohm_amd.export.plan_blend`).  One
+    candidate or alpha == 0: candidate a's bits, as `export_smplx` writes them.  disagree: the geodesic angle between the
+    candidates per joint (22 columns) and the distance of their pelvis positions; zero where there is one candidate."""
+    _lib.require_hip(repr_full, frame_clip, frame_t, frame_clip_b, frame_t_b, alpha, transf, rigid, mean, std)
+    n_clip, T, sb, st, sc = _export_args('export_smplx_blend', repr_full, layout, frame_clip, frame_t, transf, rigid, mean, std)
+    if frame_clip_b.dtype != torch.int32 or frame_t_b.dtype != torch.int32 or frame_clip_b.shape != frame_clip.shape or \
+            frame_t_b.shape != frame_clip.shape:
+        raise ValueError('frame_clip_b and frame_t_b must be int32 [N] like frame_clip')
+    if alpha.dtype != torch.float64 or alpha.shape != frame_clip.shape:
+        raise ValueError('alpha must be float64 [N]')
+    frame_clip, frame_t, frame_clip_b, frame_t_b, alpha = (t.contiguous() for t in (frame_clip, frame_t, frame_clip_b, frame_t_b, alpha))
+    N, dev = frame_clip.numel(), repr_full.device
+    params = torch.empty(N, 79, device=dev, dtype=torch.float64)
+    contact = torch.empty(N, 4, device=dev, dtype=torch.float32) if want_contact else None
+    disagree = torch.empty(N, 23, device=dev, dtype=torch.float64) if want_disagree else None
+    check(lib().rohm_export_smplx_blend(handle, C.c_void_p(repr_full.data_ptr()), sb, st, sc, ptr(mean), ptr(std), ptr(transf),
+                                        ptr(rigid), ptr(frame_clip), ptr(frame_t), ptr(frame_clip_b), ptr(frame_t_b), ptr(alpha),
+                                        n_clip, T, N, ptr(params), ptr(contact), ptr(disagree), stream_ptr(dev)),
+          'rohm_export_smplx_blend')
+    return params, contact, disagree
