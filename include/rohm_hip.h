@@ -979,6 +979,48 @@ int rohm_track_resample(const double* times_src, const int32_t* valid_idx, const
                         int n_out, double* params_out, float* keypoints_out, float* mask_out, int32_t* src_index,
                         unsigned char* gap, rohm_stream_t stream);
 
+/* Scores of a stitched track that need no ground truth (csrc/quality.hip; tests/quality_ref.py restates it).  One row per
+ * frame of the stitched track, every frame counted once.  All arrays are device memory.  joints [N,22,3] float32 in scene
+ * coordinates (ExportResult.joints with frame='scene'); up_axis 2 = z, 1 = y as in rohm_scene_metrics; has_floor /
+ * ground_height: the floor's height along up_axis; scene2cam [16] float64, row-major, with the intrinsics fx, fy, cx, cy and
+ * keypoints [N,22,3] float32 (u, v, confidence, SMPL order) -- scene2cam and keypoints are both given or both NULL;
+ * joints_ref [N,22,3] float32 (the input track in scene coordinates; may be NULL); mask_ref [N,22] float32 (1 = the joint
+ * was observed; NULL = all ones); gap [N] uint8 (NULL = all zero).  All arithmetic is float64 on the float32 inputs.
+ * rows [N,10] float64, every element written:
+ *   0 reproj_px = sum c d / sum c over the joints with c > conf_min and camera depth Z > 0, d the pixel distance between
+ *     the keypoint and (fx X / Z + cx, fy Y / Z + cy) of scene2cam . joint; NaN when no joint qualifies or without keypoints
+ *   1 reproj_max_px, the largest d over the same joints (NaN likewise)      2 the number of those joints
+ *   3 skate of the pair (t, t+1), 1 or 0: all of ankles 7, 8 and toes 10, 11 have horizontal speed > 0.10 m/s and a height
+ *     above the floor at t below 0.15 m (ankles) / 0.10 m (toes), the rule of csrc/scene_metrics.hip; NaN at the last frame
+ *     and without a floor
+ *   4 accel = mean over the 22 joints of |x[t+2] - 2 x[t+1] + x[t]| fps^2; NaN at the last two frames
+ *   5 pene = min over the two toes of min(d, 0), d = height - ground_height; NaN without a floor
+ *   6 dev_vis = mean |joints - joints_ref| over the joints with mask_ref == 1; NaN when there are none or without joints_ref
+ *   7 dev_occ, the same over mask_ref == 0      8 the number of joints with mask_ref == 1      9 gap[t] as 0 / 1
+ * A value is NaN exactly when a number it reads is not finite: a joint with c > conf_min whose camera coordinates are not
+ * finite makes 0 .. 2 NaN, a foot joint with a NaN speed or height makes 3 NaN, and so on; nothing else changes.
+ * totals [2,15] float64: the sums of group g = gap[t] (0 observed, 1 in-filled; a pair or triple belongs to the group of its
+ * first frame), NaN per-frame values left out of sums and counts:
+ *   0 frames      1 sum reproj_px      2 frames with a reproj_px      3 max reproj_max_px (NaN when 2 is 0)
+ *   4 skating pairs      5 pairs scored      6 sum accel      7 frames with an accel
+ *   8 toe entries with d < -0.05      9 sum min(d, 0) over toe entries      10 toe entries scored (a NaN d is left out)
+ *   11 sum dev_vis      12 frames with dev_vis      13 sum dev_occ      14 frames with dev_occ
+ * Two launches: half a wave per frame, then one workgroup that reduces the rows in a fixed order.  No atomics (the same
+ * input gives the same bits), no allocation, no synchronisation.  N == 0 returns without a launch. */
+int rohm_track_quality(const float* joints, int N, double fps, int up_axis, int has_floor, float ground_height,
+                       const double* scene2cam, double fx, double fy, double cx, double cy, const float* keypoints,
+                       float conf_min, const float* joints_ref, const float* mask_ref, const unsigned char* gap,
+                       double* rows, double* totals, rohm_stream_t stream);
+
+/* How far a mesh track reaches under the floor (csrc/quality.hip): toes alone miss a knee or a hand.  verts [n,V,3]
+ * float32 device memory in scene coordinates, up_axis as above.  out [n,3] float64 per frame: the lowest vertex height
+ * above the floor (height - ground_height, float64 on the float32 values), the index of that vertex (the lowest index on
+ * ties) and the number of vertices with height - ground_height < -below.  A frame with a vertex height that is not finite
+ * gets (NaN, -1, NaN).  One workgroup per frame, a fixed-order reduction; no atomics, no allocation, no synchronisation.
+ * n == 0 returns without a launch. */
+int rohm_floor_clearance(const float* verts, int n, int V, int up_axis, float ground_height, float below, double* out,
+                         rohm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -236,6 +236,9 @@ SIGNATURES = {
     'rohm_export_smplx_blend': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong] + [C.c_void_p] * 9 +
                                 [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rohm_track_resample': (C.c_int, [C.c_void_p] * 6 + [C.c_double] + [C.c_int] * 5 + [C.c_void_p] * 6),
+    'rohm_track_quality': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_float, C.c_void_p] + [C.c_double] * 4 +
+                           [C.c_void_p, C.c_float] + [C.c_void_p] * 6),
+    'rohm_floor_clearance': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
 }
 
 
