@@ -99,11 +99,14 @@ int rohm_profile_detail(int on);
  * model/posenet.py:63-69).  A, W row-major with K contiguous (lda/ldw in floats,
  * multiples of 4, 16-byte aligned); K a multiple of 32; M, N arbitrary.
  * epi: 0 = +bias, 1 = +bias, erf-form GELU (erf via A&S 7.1.26, abs err 1.5e-7), 2 = +bias +R[M,N](ldr).
- * bias may be NULL. */
+ * bias may be NULL.  Leading dimensions are in floats and may exceed the row length (views into larger matrices):
+ * lda >= K, ldw >= K, ldc >= N and, for epi 2, ldr >= N -- a shorter one would overlap rows and is refused with
+ * ROHM_ERR_ARG.  C, bias and R need no alignment and ldc / ldr no multiple (16-byte aligned ones with ldc, ldr
+ * multiples of 4 take the vector epilogue). */
 int rohm_gemm_f32(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N,
                   int K, const float* bias, const float* R, int ldr, int epi, rohm_stream_t stream);
 
-/* In-place LayerNorm over the last dimension of x[M,D] (D == 512 or 256), eps 1e-5, biased
+/* In-place LayerNorm over the last dimension of x[M,D] (D == 256, 512 or 1024), eps 1e-5, biased
  * variance, affine -- nn.LayerNorm inside nn.TransformerEncoderLayer (model/posenet.py:63-69). */
 int rohm_layernorm_f32(float* x, const float* gamma, const float* beta, int M, int D,
                        rohm_stream_t stream);

@@ -282,6 +282,19 @@ def ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def ptr_rows(t):
+    """Device pointer of a row-major 2-D HIP tensor whose rows are dense but whose row stride may exceed the row length (a view into
+    a larger matrix: the entry points that take a leading dimension); None -> NULL."""
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise RohmHipError('rohm_amd kernels need tensors on a HIP device (got CPU tensor); '
+                           'there is no CPU fallback')
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise RohmHipError('rohm_amd kernels need row-major matrices with dense rows')      # the row stride is the library's to judge
+    return C.c_void_p(t.data_ptr())
+
+
 def stream_ptr(device=None):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 

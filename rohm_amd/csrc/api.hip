@@ -114,6 +114,12 @@ int rohm_gemm_f32(const float* A, int lda, const float* W, int ldw, float* C, in
     ROHM_ARG_CHECK(A && W && C, "gemm: null pointer");
     ROHM_ARG_CHECK(epi >= EPI_BIAS && epi <= EPI_BIAS_RES, "gemm: public epilogues are 0..2 (got %d)", epi);
     ROHM_ARG_CHECK(epi != EPI_BIAS_RES || R, "gemm: epilogue 2 needs a residual");
+    // a leading dimension shorter than its row overlaps rows silently (only here: the internal launch_gemm callers pass layouts of
+    // their own, e.g. the transposed output head)
+    ROHM_ARG_CHECK(lda >= K, "gemm: lda=%d is smaller than K=%d", lda, K);
+    ROHM_ARG_CHECK(ldw >= K, "gemm: ldw=%d is smaller than K=%d", ldw, K);
+    ROHM_ARG_CHECK(ldc >= N, "gemm: ldc=%d is smaller than N=%d", ldc, N);
+    ROHM_ARG_CHECK(epi != EPI_BIAS_RES || ldr >= N, "gemm: ldr=%d is smaller than N=%d", ldr, N);
     GemmParams g{};
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
     g.bias = bias; g.R = R; g.ldr = ldr;

@@ -16,14 +16,16 @@ EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES = 0, 1, 2
 
 
 def gemm(a, w, bias=None, residual=None, epi=EPI_BIAS, out=None):
-    """out[M,N] = epi(a[M,K] @ w[N,K]^T); K must be a multiple of 32."""
+    """out[M,N] = epi(a[M,K] @ w[N,K]^T); K must be a multiple of 32.  a, w, out and residual may be views with a row stride larger
+    than their row (the entry point's lda / ldw / ldc / ldr)."""
     _lib.require_hip(a, w)
     M, K = a.shape
     N = w.shape[0]
     if out is None:
         out = torch.empty(M, N, device=a.device, dtype=torch.float32)
-    check(lib().rohm_gemm_f32(ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(out), out.stride(0), M, N, K,
-                              ptr(bias), ptr(residual), residual.stride(0) if residual is not None else 0, epi,
+    rows = _lib.ptr_rows
+    check(lib().rohm_gemm_f32(rows(a), a.stride(0), rows(w), w.stride(0), rows(out), out.stride(0), M, N, K,
+                              ptr(bias), rows(residual), residual.stride(0) if residual is not None else 0, epi,
                               stream_ptr(a.device)), 'rohm_gemm_f32')
     return out
 
@@ -84,12 +86,14 @@ def layernorm_(x, gamma, beta):
     return x
 
 
-def attention(qkv, n_seq, n_head, n_tok=144, head_dim=128):
-    """qkv [n_seq*n_tok, 3*n_head*head_dim] (q pre-scaled) -> ctx [n_seq*n_tok, n_head*head_dim]."""
-    _lib.require_hip(qkv)
+def attention(qkv, n_seq, n_head, n_tok=144, head_dim=128, out=None):
+    """qkv [n_seq*n_tok, 3*n_head*head_dim] (q pre-scaled) -> ctx [n_seq*n_tok, n_head*head_dim] (`out`, if given: contiguous)."""
+    _lib.require_hip(qkv, out)
     if qkv.shape != (n_seq * n_tok, 3 * n_head * head_dim):
         raise ValueError(f'qkv must be [{n_seq * n_tok}, {3 * n_head * head_dim}], got {tuple(qkv.shape)}')
-    ctx = torch.empty(qkv.shape[0], n_head * head_dim, device=qkv.device, dtype=torch.float32)
+    if out is not None and out.shape != (qkv.shape[0], n_head * head_dim):
+        raise ValueError(f'out must be [{qkv.shape[0]}, {n_head * head_dim}], got {tuple(out.shape)}')
+    ctx = torch.empty(qkv.shape[0], n_head * head_dim, device=qkv.device, dtype=torch.float32) if out is None else out
     check(lib().rohm_attention_f32(ptr(qkv), ptr(ctx), n_seq, n_head, n_tok, head_dim, stream_ptr(qkv.device)),
           'rohm_attention_f32')
     return ctx
