@@ -411,7 +411,8 @@ size_t rohm_trajnet_workspace_bytes(const rohm_trajnet_t* h, int B, int T);
 int rohm_trajnet_tune(int conv_wg_per_cu, int split_min_chunks, int split_pow2);
 
 /* TrajNet.forward (model/trajnet.py:177-275): x_t, cond [B, T, c_traj], control_cond [B, T, c_ctrl] (NULL
- * without TrajControl), t int64[B] -> x0_out [B, T, c_traj].  T must be a multiple of 16. */
+ * without TrajControl), t int64[B] -> x0_out [B, T, c_traj].  T must be a multiple of 16 with (mid_dim / 64) * T <= 4096, the
+ * largest GroupNorm group (T <= 512 at mid_dim 512); a longer clip returns ROHM_ERR_UNSUPPORTED before anything is launched. */
 int rohm_trajnet_forward(const rohm_trajnet_t* h, const float* x_t, const float* cond, const float* control_cond,
                          const int64_t* t, float* x0_out, int B, int T, void* ws, size_t ws_bytes,
                          rohm_stream_t stream);

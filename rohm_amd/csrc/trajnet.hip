@@ -600,6 +600,12 @@ static int check_t(const rohm_trajnet* h, int B, int T) {
     ROHM_ARG_CHECK(h != nullptr, "trajnet: null handle");
     ROHM_ARG_CHECK(B > 0, "trajnet: batch must be positive");
     ROHM_ARG_CHECK(T > 0 && T % 16 == 0, "trajnet: T must be a multiple of 16 (got %d)", T);
+    // the largest GroupNorm group is the same at every level, (mid / 64) channels x T values (the width doubles where T halves): refuse
+    // a clip that gn() would refuse behind the first convolution here, before anything is launched
+    if ((long long)(h->mid / 64) * T > 256 * kGnMaxPerThread) {
+        set_error("trajnet: GroupNorm group of %d x %d values is not supported", h->mid / 64, T);
+        return ROHM_ERR_UNSUPPORTED;
+    }
     return ROHM_OK;
 }
 

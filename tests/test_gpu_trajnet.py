@@ -16,10 +16,11 @@ class Args:
     noise_schedule, sigma_small = 'cosine', True
 
 
-def make_trajnet(seed, ctrl):
+def make_trajnet(seed, ctrl, ct=13, cc=272):
+    """ct / cc: traj_feat_dim (= cond_dim) and control_cond_dim; the defaults are the drivers' repr_abs_only=True widths."""
     from rohm_amd.model.trajnet import TrajNet
-    net = TrajNet(time_dim=32, mid_dim=512, cond_dim=13, traj_feat_dim=13, trajcontrol=ctrl, device=DEV)
-    sd = synth.trajnet_state_dict(seed, trajcontrol=ctrl)
+    net = TrajNet(time_dim=32, mid_dim=512, cond_dim=ct, traj_feat_dim=ct, trajcontrol=ctrl, control_cond_dim=cc, device=DEV)
+    sd = synth.trajnet_state_dict(seed, traj_feat_dim=ct, cond_dim=ct, trajcontrol=ctrl, control_cond_dim=cc)
     net.load_state_dict(sd, strict=True)
     return net.to(DEV).eval(), sd
 
@@ -217,8 +218,8 @@ def test_large_batch_is_clip_independent():
 
 # ---- the clip-resident step (csrc/trajnet_resident.hip): one launch per denoising step; default for TrajNet, ROHM_TRAJ_RESIDENT=1 for TrajControl ----
 
-def _loop(net, batch, shape, x_T, noises, fused_chunk=None):
-    diff = make_diffusion()
+def _loop(net, batch, shape, x_T, noises, fused_chunk=None, steps=100):
+    diff = make_diffusion(steps)
     diff.noise_source = lambda step, like: (x_T if step == -1 else noises[step])
     if fused_chunk:
         diff.fused_chunk = fused_chunk

@@ -23,15 +23,17 @@ ABS_CH = [0, 2, 3, 6, 7, 8, 9, 10, 11, 12, 16, 17, 18]
 UNUSED = ('cond_downsample4.conv.weight', 'cond_downsample4.conv.bias')
 
 
-def make_net(ctrl, seed=0, zero_convs_random=True, **kw):
-    net = TrajNet(time_dim=32, mid_dim=512, cond_dim=13, traj_feat_dim=13, trajcontrol=ctrl, device=DEV, **kw)
-    sd = synth.trajnet_state_dict(seed, trajcontrol=ctrl, zero_convs_random=zero_convs_random)
+def make_net(ctrl, seed=0, zero_convs_random=True, ct=13, cc=272, **kw):
+    """ct / cc: traj_feat_dim (= cond_dim) and control_cond_dim; the defaults are the drivers' repr_abs_only=True widths."""
+    net = TrajNet(time_dim=32, mid_dim=512, cond_dim=ct, traj_feat_dim=ct, trajcontrol=ctrl, control_cond_dim=cc, device=DEV, **kw)
+    sd = synth.trajnet_state_dict(seed, traj_feat_dim=ct, cond_dim=ct, trajcontrol=ctrl, control_cond_dim=cc,
+                                  zero_convs_random=zero_convs_random)
     net.load_state_dict(sd, strict=True)
     return net.to(DEV).train(), sd
 
 
-def inputs(B, T, seed=1):
-    x, c, cc, cot = seeded(seed, B, T, 13), seeded(seed + 1, B, T, 13), seeded(seed + 2, B, T, 272), seeded(seed + 3, B, T, 13)
+def inputs(B, T, seed=1, ct=13, cc=272):
+    x, c, cc, cot = seeded(seed, B, T, ct), seeded(seed + 1, B, T, ct), seeded(seed + 2, B, T, cc), seeded(seed + 3, B, T, ct)
     t = torch.tensor([(37 * i + 3) % 100 for i in range(B)])      # per-sample distinct (up to B = 100)
     return x, c, cc, t, cot
 
@@ -40,8 +42,8 @@ def rel(a, ref):
     return float((a.detach().double().cpu() - ref.double()).norm() / ref.double().norm().clamp_min(1e-30))
 
 
-def names(ctrl):
-    return weight_order(512, 13, ctrl)
+def names(ctrl, ct=13):
+    return weight_order(512, ct, ctrl)
 
 
 def ref_grads(sd, x, c, cc, t, cot, ctrl, loss_fn=None):
@@ -54,7 +56,7 @@ def ref_grads(sd, x, c, cc, t, cot, ctrl, loss_fn=None):
     return out.detach(), {k: v.grad for k, v in sdg.items()}, xg.grad, cg.grad, (kg.grad if ctrl else None)
 
 
-def device_grads(net, x, c, cc, t, cot, ctrl, input_grads=True):
+def device_grads(net, x, c, cc, t, cot, ctrl, input_grads=True, ct=13):
     xg = x.to(DEV).requires_grad_(input_grads)
     cg = c.to(DEV).requires_grad_(input_grads)
     kg = cc.to(DEV).requires_grad_(input_grads)
@@ -63,14 +65,14 @@ def device_grads(net, x, c, cc, t, cot, ctrl, input_grads=True):
     assert out.grad_fn is not None
     (out * cot.to(DEV)).sum().backward()
     named = dict(net.named_parameters())
-    return out.detach(), {k: named[k].grad for k in names(ctrl)}, xg.grad, cg.grad, (kg.grad if ctrl else None)
+    return out.detach(), {k: named[k].grad for k in names(ctrl, ct)}, xg.grad, cg.grad, (kg.grad if ctrl else None)
 
 
-def check_all(dev, ref, ctrl, label=''):
+def check_all(dev, ref, ctrl, label='', ct=13):
     _, g, dx, dc, dk = dev
     _, g64, dx64, dc64, dk64 = ref
     worst = ('', 0.0)
-    for k in names(ctrl):
+    for k in names(ctrl, ct):
         if k in UNUSED:
             assert g[k] is None and g64[k] is None, k
             continue
@@ -84,6 +86,7 @@ def check_all(dev, ref, ctrl, label=''):
         print(f'{label} {name}: rel {e:.3e}')
         assert e <= REL_BAR, (name, e)
     print(f'{label} worst parameter {worst}')
+    return worst
 
 
 # ------------------------------------------------------------------------------ 1. gradients against float64 autograd
