@@ -1025,6 +1025,45 @@ int rohm_track_quality(const float* joints, int N, double fps, int up_axis, int 
 int rohm_floor_clearance(const float* verts, int n, int V, int up_axis, float ground_height, float below, double* out,
                          rohm_stream_t stream);
 
+/* The floor of an uncalibrated camera-frame track (csrc/floor.hip; rohm_amd/floor.py drives the three entry points,
+ * tests/floor_ref.py restates them).  No counterpart in the reference.  All arrays are device memory, all arithmetic is
+ * float64 on the float32 positions, no atomics (the same input gives the same bits), no allocation.
+ *
+ * rohm_floor_candidates: which toe positions are at rest.  joints [N,22,3] float32 in the camera frame, times [N] float64
+ * seconds (strictly increasing), valid_idx [Nv] int32, the ascending indices of the frames that have a fit, keypoints
+ * [N,22,3] float32 (x, y, confidence; may be NULL).  flags [N,2] uint8 for the toes (joints 10 and 11), every element
+ * written: flags[i][k] = 1 exactly when frame i is in valid_idx and has a successor i' there with
+ * 0 < dt = times[i'] - times[i] <= max_gap, |p[i'] - p[i]| / dt < v_max (p the toe's position) and, with keypoints, the
+ * toe's confidence at i > conf_min.  A number that is not finite anywhere in the rule gives 0.  An entry of valid_idx
+ * outside [0, N), or one whose successor is not larger, marks nothing and reads nothing.  Two launches, no
+ * synchronisation.  N == 0 returns without a launch. */
+int rohm_floor_candidates(const float* joints, const double* times, const int32_t* valid_idx, const float* keypoints, int N,
+                          int Nv, float conf_min, double v_max, double max_gap, unsigned char* flags, rohm_stream_t stream);
+
+/* rohm_floor_hypotheses: K candidate planes scored in one launch.  points [P,3] float32 (the resting toe positions), joints
+ * [NJ,3] float32 (every joint of every valid frame), triples [K,3] int32 indices into points (read back and checked here:
+ * one stream synchronisation per call; an index outside [0, P) is refused by name).  For hypothesis h with the points p0,
+ * p1, p2 of its triple: n = (p1 - p0) x (p2 - p0); the triple is degenerate unless 1e-9 <= |n| < inf; n /= |n|,
+ * d = -n . p0.  pos = #(n . q + d > under_tol) and neg = #(n . q + d < -under_tol) over the joints q; if neg > pos the plane
+ * is turned over (n, d -> -n, -d) and the counts change places, a tie keeps it.  under = neg, support =
+ * #(|n . p + d| <= tau) over the points, score = support - under.  planes [K,4] float64 (n, d); scores [K,3] int64 (score,
+ * support, under); a degenerate triple gets a NaN plane and (INT64_MIN, 0, 0).  best [1] int32: the hypothesis with the
+ * largest score, the lowest index on ties, -1 when every triple is degenerate.  A NaN position fails every comparison and
+ * so is in no count.  All counts are integers: no reduction order can change a bit.  Two launches (16 hypotheses per
+ * workgroup, positions tiled through LDS; then one workgroup for best).  K == 0 returns without a launch; K > 0 needs
+ * P >= 3. */
+int rohm_floor_hypotheses(const float* points, int P, const float* joints, int NJ, const int32_t* triples, int K, double tau,
+                          double under_tol, double* planes, long long* scores, int32_t* best, rohm_stream_t stream);
+
+/* rohm_floor_moments: the sums a least-squares plane through the inliers needs.  points [P,3] float32, plane [4] float64
+ * (n, d), origin [3] float64 (any point near the inliers; it keeps the products small).  Over the points with
+ * |r| <= tau, r = n . p + d, and q = p - origin: out [11] float64 = count, sum q (x, y, z), sum of the products xx, xy, xz,
+ * yy, yz, zz of q, sum r^2.  A NaN position is no inlier.  One workgroup of 1024 threads, a fixed order (as the totals of
+ * rohm_track_quality): thread t takes the points t, t + 1024, ..., a xor-butterfly per wave, then the 16 wave partials in
+ * wave order.  No workspace, no synchronisation.  P == 0 returns without a launch and leaves out alone. */
+int rohm_floor_moments(const float* points, int P, const double* plane, const double* origin, double tau, double* out,
+                       rohm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -239,6 +239,10 @@ SIGNATURES = {
     'rohm_track_quality': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_float, C.c_void_p] + [C.c_double] * 4 +
                            [C.c_void_p, C.c_float] + [C.c_void_p] * 6),
     'rohm_floor_clearance': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    'rohm_floor_candidates': (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    'rohm_floor_hypotheses': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double] +
+                              [C.c_void_p] * 4),
+    'rohm_floor_moments': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
 }
 
 
