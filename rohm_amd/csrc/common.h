@@ -41,6 +41,8 @@ void set_error(const char* fmt, ...);
         }                                                                                \
     } while (0)
 
+inline bool aligned16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
+
 // ---- in-library launch profiler (HIP events on the launch stream; see rohm_profile_* in rohm_hip.h) --
 namespace prof {
 extern bool g_active;          // true while this launch should be bracketed

@@ -4,7 +4,7 @@
 // parameters, so an optimiser step needs no rebuild of anything.
 //
 // All products run on one strided, batched fp32-MFMA GEMM (v_mfma_f32_16x16x4_f32, exact fp32 fma chains like the rest of the
-// library).  Its operands are addressed through (row, column, batch) strides, so the transposed operands of the backward -- the
+// library; the tile and its pipeline are train_tile.h).  Its operands are addressed through (row, column, batch) strides, so the transposed operands of the backward -- the
 // reduction axis of a weight gradient is the token axis, the attention's dK / dV contract over queries -- are staged through LDS
 // transposed instead of being materialised, and the [B, C, 1, T] channel-major tensors of the embeds and the output head are read
 // and written in place.  Weight gradients split their token axis into slices of kRowsPerSplit rows that go to their own
@@ -22,6 +22,7 @@ namespace rohm {
 namespace {
 
 #include "train_reduce.h"
+#include "train_tile.h"
 
 constexpr int kD = 512, kH = 4, kF = 1024, kDh = 128, kMaxS = 145;
 constexpr int kRowsPerSplit = 576;      // token rows per weight-gradient slice: 4 clips of 144 tokens, but any M goes -- a slice may cut a
@@ -68,8 +69,6 @@ struct TG {
     Drop drop;
 };
 
-constexpr int TBM = 64, TBN = 64, TBK = 32, LDP = TBM + 16;      // +16: the 4 k-rows of a fragment read hit distinct bank groups
-
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
 __device__ __forceinline__ float silu_grad(float x) {
     const float s = 1.0f / (1.0f + expf(-x));
@@ -80,9 +79,8 @@ __device__ __forceinline__ float gelu_grad(float x) {      // d/dx 0.5 x (1 + er
 }
 
 __global__ __launch_bounds__(256) void tgemm_kernel(TG p) {
-    __shared__ float As[TBK * LDP];      // [k][m]
-    __shared__ float Bs[TBK * LDP];      // [k][n]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ float As[kStageFloats];      // [k][m]
+    __shared__ float Bs[kStageFloats];      // [k][n]
     const int n0 = blockIdx.x * TBN, m0 = blockIdx.y * TBM;
     const int z1 = blockIdx.z / p.nb2, z2 = blockIdx.z % p.nb2;
     const float* A = p.A + z1 * p.a_b1 + z2 * p.a_b2;
@@ -95,58 +93,30 @@ __global__ __launch_bounds__(256) void tgemm_kernel(TG p) {
     // global -> register staging: threads run along whichever axis of the operand is contiguous
     const bool a_kc = (p.a_cs == 1), b_nc = (p.b_cs == 1);
     float ra[8], rb[8];
-    auto a_at = [&](int e, int& m, int& k) __attribute__((always_inline)) {
-        const int lin = e * 256 + tid;
-        if (a_kc) { k = lin & 31; m = lin >> 5; } else { m = lin & 63; k = lin >> 6; }
-    };
-    auto b_at = [&](int e, int& k, int& n) __attribute__((always_inline)) {
-        const int lin = e * 256 + tid;
-        if (b_nc) { n = lin & 63; k = lin >> 6; } else { k = lin & 31; n = lin >> 5; }
-    };
-    auto load = [&](int k0) __attribute__((always_inline)) {
+    Tile t;
+    t.run<TBK>(As, Bs, 0, kend,
+        [&](int k0) __attribute__((always_inline)) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            int m, k, kb, n;
-            a_at(e, m, k);
-            b_at(e, kb, n);
-            const int gm = m0 + m, gk = k0 + k, gn = n0 + n, gkb = k0 + kb;
-            ra[e] = (gm < p.M && gk < kend) ? A[gm * p.a_rs + gk * p.a_cs] : 0.f;
-            rb[e] = (gn < p.N && gkb < kend) ? Bp[gkb * p.b_rs + gn * p.b_cs] : 0.f;
-        }
-    };
-    f32x4 acc[2][2];
+            for (int e = 0; e < 8; ++e) {
+                int m, k, kb, n;
+                stage_map(!a_kc, e, k, m);
+                stage_map(b_nc, e, kb, n);
+                const int gm = m0 + m, gk = k0 + k, gn = n0 + n, gkb = k0 + kb;
+                ra[e] = (gm < p.M && gk < kend) ? A[gm * p.a_rs + gk * p.a_cs] : 0.f;
+                rb[e] = (gn < p.N && gkb < kend) ? Bp[gkb * p.b_rs + gn * p.b_cs] : 0.f;
+            }
+        },
+        [&]() __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
-    const int li = lane & 15, lk = lane >> 4;
-    if (kend > 0) load(0);
-    for (int k0 = 0; k0 < kend; k0 += TBK) {
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            int m, k, kb, n;
-            a_at(e, m, k);
-            b_at(e, kb, n);
-            As[k * LDP + m] = ra[e];
-            Bs[kb * LDP + n] = rb[e];
-        }
-        __syncthreads();
-        if (k0 + TBK < kend) load(k0 + TBK);      // lands under this chunk's MFMAs
-#pragma unroll
-        for (int kk = 0; kk < TBK; kk += 4) {
-            const float* ar = As + (kk + lk) * LDP;
-            const float* br = Bs + (kk + lk) * LDP;
-            const float a0 = ar[wm + li], a1 = ar[wm + 16 + li];
-            const float b0 = br[wn + li], b1 = br[wn + 16 + li];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-    }
-    // acc[i][j][r] = C(m0 + wm + 16 i + 4 lk + r, n0 + wn + 16 j + li)
+            for (int e = 0; e < 8; ++e) {
+                int m, k, kb, n;
+                stage_map(!a_kc, e, k, m);
+                stage_map(b_nc, e, kb, n);
+                As[stage_at(k, m)] = ra[e];
+                Bs[stage_at(kb, n)] = rb[e];
+            }
+        });
+    const auto& acc = t.acc;
     const long long cbase = z1 * p.c_b1 + z2 * p.c_b2;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -154,7 +124,7 @@ __global__ __launch_bounds__(256) void tgemm_kernel(TG p) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int m = m0 + wm + 16 * i + 4 * lk + r, n = n0 + wn + 16 * j + li;
+                const int m = m0 + t.row(i, r), n = n0 + t.col(j);
                 if (m >= p.M || n >= p.N) continue;
                 float v = acc[i][j][r] * p.alpha;
                 if (p.bias) v += p.bias[n];
@@ -480,15 +450,10 @@ int weight_grad(const float* dY, long long ldy, const float* X, long long ldx, i
     TG p = tg_plain();
     p.A = dY; p.a_rs = 1; p.a_cs = ldy; p.a_b1 = (long long)kRowsPerSplit * ldy;
     p.B = X; p.b_rs = ldx; p.b_cs = 1; p.b_b1 = (long long)kRowsPerSplit * ldx;
-    p.C = ns > 1 ? part : dW; p.c_rs = K; p.c_cs = 1; p.c_b1 = (long long)N * K;
+    p.c_rs = K; p.c_cs = 1; p.c_b1 = (long long)N * K;
     p.M = N; p.N = K; p.K = kRowsPerSplit; p.k_total = M; p.nb1 = ns;
-    int rc = launch_tg(p, "train_wgrad", s);
+    int rc = slab_sum(ns, p.c_b1, part, dW, s, [&](float* dst) { p.C = dst; return launch_tg(p, "train_wgrad", s); });
     if (rc) return rc;
-    if (ns > 1) {
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3(blocks((long long)N * K, 256)), dim3(256), 0, s, part, ns, (long long)N * K, dW,
-                           (float*)nullptr);
-        ROHM_LAUNCH_CHECK();
-    }
     if (db) return colsum(dY, 0, M, ldy, 1, M, N, db, nullptr, cpart, s);
     return ROHM_OK;
 }
@@ -508,7 +473,7 @@ static int train_forward(const rohm_posenet_weights* w, const Dims& d, const flo
                          float dropout_p, unsigned long long seed, float* out, float* sv, hipStream_t s) {
     const SavedLayout o = saved_layout(d);
     const int D = d.D, F = d.F, M = d.M, S = d.S, T = d.T, B = d.B, H = d.H;
-    const long long CT = (long long)d.c_in * T, PS = (long long)B * H * S * S;
+    const long long CT = (long long)d.c_in * T;
     const float qscale = 1.0f / sqrtf((float)kDh);
     int rc;
     // ---- timestep token: pe[t] -> Linear -> SiLU -> Linear (model/heads.py:140-146)
@@ -563,7 +528,6 @@ static int train_forward(const rohm_posenet_weights* w, const Dims& d, const flo
         p.C = ctx; p.c_rs = D; p.c_cs = 1; p.c_b1 = (long long)S * D; p.c_b2 = kDh;
         p.M = S; p.N = kDh; p.K = S;
         if ((rc = launch_tg(p, "train_attn_pv", s))) return rc;
-        (void)PS;
         // s1 = x + dropout1(out_proj(ctx)); y = norm1(s1)
         p = tg_nt(ctx, lw.out_proj_w, L0 + o.s1, M, D, D);
         p.bias = lw.out_proj_b; p.drop = make_drop(dropout_p, seed, l, 2); p.R = x;
@@ -618,14 +582,9 @@ static int train_backward(const rohm_posenet_weights* w, const Dims& d, const fl
     p = tg_plain();
     p.A = d_out + (long long)d.traj * T; p.a_rs = T; p.a_cs = 1; p.a_b1 = CT;
     p.B = sv + o.hL + D; p.b_rs = D; p.b_cs = 1; p.b_b1 = (long long)S * D;
-    p.C = B > 1 ? part : g->out_w; p.c_rs = D; p.c_cs = 1; p.c_b1 = (long long)d.c_out * D;
-    p.M = d.c_out; p.N = D; p.K = T; p.nb1 = B;
-    if ((rc = launch_tg(p, "train_wgrad_head", s))) return rc;
-    if (B > 1) {
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3(blocks((long long)d.c_out * D, 256)), dim3(256), 0, s, part, B,
-                           (long long)d.c_out * D, g->out_w, (float*)nullptr);
-        ROHM_LAUNCH_CHECK();
-    }
+    p.c_rs = D; p.c_cs = 1; p.c_b1 = (long long)d.c_out * D;
+    p.M = d.c_out; p.N = D; p.K = T; p.nb1 = B;      // one slab per clip
+    if ((rc = slab_sum(B, p.c_b1, part, g->out_w, s, [&](float* dst) { p.C = dst; return launch_tg(p, "train_wgrad_head", s); }))) return rc;
     if ((rc = colsum(d_out + (long long)d.traj * T, CT, T, 1, T, B * T, d.c_out, g->out_b, nullptr, cpart, s))) return rc;
     // ---- encoder layers, last to first; dh = gradient of the layer's output
     for (int l = d.L - 1; l >= 0; --l) {
@@ -734,14 +693,11 @@ static int train_backward(const rohm_posenet_weights* w, const Dims& d, const fl
         p = tg_plain();
         p.A = dh + D; p.a_rs = 1; p.a_cs = D; p.a_b1 = (long long)S * D;
         p.B = src; p.b_rs = 1; p.b_cs = T; p.b_b1 = CT;
-        p.C = B > 1 ? part : (half ? g->in_c_w : g->in_x_w); p.c_rs = d.c_in; p.c_cs = 1; p.c_b1 = (long long)D * d.c_in;
-        p.M = D; p.N = d.c_in; p.K = T; p.nb1 = B;
-        if ((rc = launch_tg(p, "train_wgrad_embed", s))) return rc;
-        if (B > 1) {
-            hipLaunchKernelGGL(reduce_slabs_kernel, dim3(blocks((long long)D * d.c_in, 256)), dim3(256), 0, s, part, B,
-                               (long long)D * d.c_in, half ? g->in_c_w : g->in_x_w, (float*)nullptr);
-            ROHM_LAUNCH_CHECK();
-        }
+        p.c_rs = d.c_in; p.c_cs = 1; p.c_b1 = (long long)D * d.c_in;
+        p.M = D; p.N = d.c_in; p.K = T; p.nb1 = B;      // one slab per clip
+        rc = slab_sum(B, p.c_b1, part, half ? g->in_c_w : g->in_x_w, s,
+                      [&](float* slabs) { p.C = slabs; return launch_tg(p, "train_wgrad_embed", s); });
+        if (rc) return rc;
         float* dst = half ? d_cond : d_x_t;
         if (!dst) continue;
         p = tg_plain();
@@ -762,8 +718,6 @@ static int train_backward(const rohm_posenet_weights* w, const Dims& d, const fl
 }  // namespace rohm
 
 using namespace rohm;
-
-static bool aligned16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
 
 extern "C" size_t rohm_posenet_train_saved_bytes(int d_model, int n_head, int d_ff, int n_layer, int c_in, int c_out, int B, int T) {
     Dims d;

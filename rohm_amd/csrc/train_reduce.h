@@ -1,5 +1,5 @@
 // Deterministic reductions shared by the two training sources (posenet_train.hip, trajnet_train.hip): column sums in row chunks and
-// the in-order sum of partial slabs.  No float atomics: a gradient summed here is bitwise reproducible.  Included inside each
+// the in-order sum of partial slabs (slab_sum).  No float atomics: a gradient summed here is bitwise reproducible.  Included inside each
 // source's anonymous namespace.
 #pragma once
 
@@ -33,6 +33,17 @@ __global__ void reduce_slabs_kernel(const float* __restrict__ part, int S, long 
     for (int k = 1; k < S; ++k) s += part[(long long)k * n + i];
     out[i] = s;
     if (out2) out2[i] = s;
+}
+
+// A product split into ns partial slabs of n floats each, then summed in slab order into out: product(dst) launches the GEMM that
+// writes slab s at dst + s n.  A single slab is written straight to out, with no second launch.
+template <class Product>
+inline int slab_sum(int ns, long long n, float* part, float* out, hipStream_t s, Product product) {
+    const int rc = product(ns > 1 ? part : out);
+    if (rc || ns <= 1) return rc;
+    hipLaunchKernelGGL(reduce_slabs_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, part, ns, n, out, (float*)nullptr);
+    ROHM_LAUNCH_CHECK();
+    return ROHM_OK;
 }
 
 inline int colsum(const float* X, long long outer_stride, int inner, long long inner_stride, long long col_stride, int rows, int N,

@@ -9,7 +9,7 @@
 // (T_l = T >> l).  A convolution is then a GEMM over the flattened rows whose A operand is read at a row offset per tap -- no
 // gather and no boundary predicate inside a clip -- and whose epilogue stores zeros on the halo rows, so every buffer is written
 // whole by the kernel that produces it.  The stride-2 convs map output rows to input rows with a factor of two (the transposed
-// conv as two phases).  Two kernels carry all products, on v_mfma_f32_16x16x4_f32 (exact fp32 fma chains):
+// conv as two phases).  Two kernels carry all products, on the tile of train_tile.h (v_mfma_f32_16x16x4_f32, exact fp32 fma chains):
 //   cgemm_kernel  Y = taps(X) . W    forward convs, data gradients (taps mirrored / phases swapped), the Linears of the time path;
 //                 the weights are read in place through (tap, k, n) strides;
 //   wgemm_kernel  dW = dY^T . taps(X) over a slab of whole clips, one tap per grid slice; slabs are added in index order afterwards.
@@ -22,10 +22,10 @@ namespace rohm {
 namespace {
 
 #include "train_reduce.h"
+#include "train_tile.h"
 
 constexpr int kGroups = 8, kHalo = 2, kTdim = 32, kMid = 512;
 constexpr int kSlabRows = 512;          // rows per weight-gradient slab (rounded down to whole clips, at least one)
-constexpr int TBM = 64, TBN = 64, TBK = 32, LDP = TBM + 16;
 
 // d/dx mish(x) from the e = exp(min(x, 20)), n = e (e + 2) form of mishf: mish = x n / (n + 2), (n / (n + 2))' = 4 e (e + 1) / (n + 2)^2
 __device__ __forceinline__ float mish_grad(float x) {
@@ -54,24 +54,10 @@ struct CG {
     int accumulate;
 };
 
-__device__ __forceinline__ void mfma_chunk(const float* As, const float* Bs, f32x4 (&acc)[2][2], int wm, int wn, int li, int lk) {
-#pragma unroll
-    for (int kk = 0; kk < TBK; kk += 4) {
-        const float* ar = As + (kk + lk) * LDP;
-        const float* br = Bs + (kk + lk) * LDP;
-        const float a0 = ar[wm + li], a1 = ar[wm + 16 + li];
-        const float b0 = br[wn + li], b1 = br[wn + 16 + li];
-        acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-}
-
 __global__ __launch_bounds__(256) void cgemm_kernel(CG p) {
-    __shared__ float As[TBK * LDP];      // [k][m]
-    __shared__ float Bs[TBK * LDP];      // [k][n]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ float As[kStageFloats];      // [k][m]
+    __shared__ float Bs[kStageFloats];      // [k][n]
+    const int tid = threadIdx.x;
     const int n0 = blockIdx.x * TBN, m0 = blockIdx.y * TBM;
     // A: threads run along k (contiguous); each thread owns 8 rows whose clip-mapped row index is fixed across the reduction
     const int ak = tid & 31;
@@ -85,52 +71,38 @@ __global__ __launch_bounds__(256) void cgemm_kernel(CG p) {
     const bool b_nfast = p.b_cs <= p.b_rs;
     const int kchunks = (p.K + TBK - 1) / TBK, iters = p.ntap * kchunks;
     float ra[8], rb[8];
-    auto b_at = [&](int e, int& k, int& n) __attribute__((always_inline)) {
-        const int lin = e * 256 + tid;
-        if (b_nfast) { n = lin & 63; k = lin >> 6; } else { k = lin & 31; n = lin >> 5; }
-    };
-    auto load = [&](int it) __attribute__((always_inline)) {
-        const int tap = it / kchunks, k0 = (it - tap * kchunks) * TBK;
-        const float* Bt = p.B + tap * p.b_ts;
-        const long long roff = (long long)tap * p.a_qt;
-        const int gk = k0 + ak;
+    Tile t;
+    t.run<1>(As, Bs, 0, iters,
+        [&](int it) __attribute__((always_inline)) {
+            const int tap = it / kchunks, k0 = (it - tap * kchunks) * TBK;
+            const float* Bt = p.B + tap * p.b_ts;
+            const long long roff = (long long)tap * p.a_qt;
+            const int gk = k0 + ak;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const long long r = arow[e] + roff;
-            ra[e] = (gk < p.K && r >= 0 && r < p.a_rows) ? p.A[r * p.lda + gk] : 0.f;
-            int kb, n;
-            b_at(e, kb, n);
-            const int gkb = k0 + kb, gn = n0 + n;
-            rb[e] = (gkb < p.K && gn < p.N) ? Bt[gkb * p.b_rs + gn * p.b_cs] : 0.f;
-        }
-    };
-    f32x4 acc[2][2];
+            for (int e = 0; e < 8; ++e) {
+                const long long r = arow[e] + roff;
+                ra[e] = (gk < p.K && r >= 0 && r < p.a_rows) ? p.A[r * p.lda + gk] : 0.f;
+                int kb, n;
+                stage_map(b_nfast, e, kb, n);
+                const int gkb = k0 + kb, gn = n0 + n;
+                rb[e] = (gkb < p.K && gn < p.N) ? Bt[gkb * p.b_rs + gn * p.b_cs] : 0.f;
+            }
+        },
+        [&]() __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
-    const int li = lane & 15, lk = lane >> 4;
-    if (iters > 0) load(0);
-    for (int it = 0; it < iters; ++it) {
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            int kb, n;
-            b_at(e, kb, n);
-            As[ak * LDP + e * 8 + (tid >> 5)] = ra[e];
-            Bs[kb * LDP + n] = rb[e];
-        }
-        __syncthreads();
-        if (it + 1 < iters) load(it + 1);      // lands under this chunk's MFMAs
-        mfma_chunk(As, Bs, acc, wm, wn, li, lk);
-    }
-    // acc[i][j][r] = C(m0 + wm + 16 i + 4 lk + r, n0 + wn + 16 j + li)
+            for (int e = 0; e < 8; ++e) {
+                int kb, n;
+                stage_map(b_nfast, e, kb, n);
+                As[stage_at(ak, e * 8 + (tid >> 5))] = ra[e];
+                Bs[stage_at(kb, n)] = rb[e];
+            }
+        });
+    const auto& acc = t.acc;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int m = m0 + wm + 16 * i + 4 * lk + r;
+            const int m = m0 + t.row(i, r);
             if (m >= p.M) continue;
             const int oq = (m % p.mdiv) * p.c_qm + p.c_qo;
             if (oq < 0 || oq >= p.c_tp) continue;
@@ -138,7 +110,7 @@ __global__ __launch_bounds__(256) void cgemm_kernel(CG p) {
             const long long crow = ((long long)(m / p.mdiv) * p.c_tp + oq) * p.ldc;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const int n = n0 + wn + 16 * j + li;
+                const int n = n0 + t.col(j);
                 if (n >= p.N) continue;
                 const long long ci = crow + n;
                 float v = acc[i][j][r];
@@ -164,49 +136,40 @@ struct WG {
 };
 
 __global__ __launch_bounds__(256) void wgemm_kernel(WG p) {
-    __shared__ float As[TBK * LDP];      // [row][i]
-    __shared__ float Bs[TBK * LDP];      // [row][j]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ float As[kStageFloats];      // [row][i]
+    __shared__ float Bs[kStageFloats];      // [row][j]
+    const int tid = threadIdx.x;
     const int j0 = blockIdx.x * TBN, i0 = blockIdx.y * TBM;
     const int slab = blockIdx.z / p.ntap, tap = blockIdx.z % p.ntap;
     const int mbeg = slab * p.ms, mend = (mbeg + p.ms < p.M) ? mbeg + p.ms : p.M;
     const int c = tid & 63, kr = tid >> 6;      // threads run along the channels (contiguous); 4 rows per pass, 8 passes per chunk
     float ra[8], rb[8];
-    auto load = [&](int mb) __attribute__((always_inline)) {
+    Tile t;
+    t.run<TBK>(As, Bs, mbeg, mend,
+        [&](int mb) __attribute__((always_inline)) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int m = mb + e * 4 + kr;
-            float a = 0.f, b = 0.f;
-            if (m < mend) {
-                const int cb = m / p.mdiv, q = m - cb * p.mdiv;
-                const long long rl = (long long)cb * p.l_tp + q + p.l_qo;
-                const long long rp = (long long)cb * p.p_tp + (long long)q * p.p_qm + p.p_qo + tap;
-                if (i0 + c < p.I && rl >= 0 && rl < p.l_rows) a = p.L[rl * p.ldl + i0 + c];
-                if (j0 + c < p.J && rp >= 0 && rp < p.p_rows) b = p.P[rp * p.ldp + j0 + c];
+            for (int e = 0; e < 8; ++e) {
+                const int m = mb + e * 4 + kr;
+                float a = 0.f, b = 0.f;
+                if (m < mend) {
+                    const int cb = m / p.mdiv, q = m - cb * p.mdiv;
+                    const long long rl = (long long)cb * p.l_tp + q + p.l_qo;
+                    const long long rp = (long long)cb * p.p_tp + (long long)q * p.p_qm + p.p_qo + tap;
+                    if (i0 + c < p.I && rl >= 0 && rl < p.l_rows) a = p.L[rl * p.ldl + i0 + c];
+                    if (j0 + c < p.J && rp >= 0 && rp < p.p_rows) b = p.P[rp * p.ldp + j0 + c];
+                }
+                ra[e] = a;
+                rb[e] = b;
             }
-            ra[e] = a;
-            rb[e] = b;
-        }
-    };
-    f32x4 acc[2][2];
+        },
+        [&]() __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
-    const int li = lane & 15, lk = lane >> 4;
-    if (mbeg < mend) load(mbeg);
-    for (int mb = mbeg; mb < mend; mb += TBK) {
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            As[(e * 4 + kr) * LDP + c] = ra[e];
-            Bs[(e * 4 + kr) * LDP + c] = rb[e];
-        }
-        __syncthreads();
-        if (mb + TBK < mend) load(mb + TBK);
-        mfma_chunk(As, Bs, acc, wm, wn, li, lk);
-    }
+            for (int e = 0; e < 8; ++e) {
+                As[stage_at(e * 4 + kr, c)] = ra[e];
+                Bs[stage_at(e * 4 + kr, c)] = rb[e];
+            }
+        });
+    const auto& acc = t.acc;
     float* G = p.G + (long long)slab * p.g_slab + tap;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -214,7 +177,7 @@ __global__ __launch_bounds__(256) void wgemm_kernel(WG p) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int gi = i0 + wm + 16 * i + 4 * lk + r, gj = j0 + wn + 16 * j + li;
+                const int gi = i0 + t.row(i, r), gj = j0 + t.col(j);
                 if (gi < p.I && gj < p.J) G[gi * p.g_is + gj * p.g_js] = acc[i][j][r];
             }
 }
@@ -720,18 +683,14 @@ int launch_wg(Ctx& c, WG p, float* dW, long long wsize, int nclips, const char* 
         set_error("trajnet training: weight-gradient slabs exceed the scratch plan (%d x %lld floats)", ns, wsize);
         return ROHM_ERR_ARG;
     }
-    p.G = ns > 1 ? c.sc->part : dW;
-    {
+    return slab_sum(ns, wsize, c.sc->part, dW, c.s, [&](float* dst) -> int {
+        p.G = dst;
         prof::Scope ps(label, 2.0 * p.I * p.J * (double)p.M * p.ntap, 0.0, c.s);
         hipLaunchKernelGGL(wgemm_kernel, dim3((p.J + TBN - 1) / TBN, (p.I + TBM - 1) / TBM, ns * p.ntap), dim3(256), 0, c.s, p);
         ROHM_LAUNCH_CHECK();
         ++c.gemms;
-    }
-    if (ns > 1) {
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3(blocks(wsize, 256)), dim3(256), 0, c.s, c.sc->part, ns, wsize, dW, (float*)nullptr);
-        ROHM_LAUNCH_CHECK();
-    }
-    return ROHM_OK;
+        return ROHM_OK;
+    });
 }
 // Gradients of a Conv1d's weight [C_out, C_in, k] and bias: dy at level ly (rows of the reduction), x at level lx; stride = 1 or 2
 int conv_wgrad(Ctx& c, const ConvP& w, View dy, int ly, View x, int lx, int stride) {
@@ -1088,8 +1047,6 @@ std::atomic<int> g_last_gemms{0};      // autograd runs the backward on a thread
 }  // namespace rohm
 
 using namespace rohm;
-
-static bool aligned16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
 
 extern "C" size_t rohm_trajnet_train_saved_bytes(int mid_dim, int time_dim, int c_traj, int c_ctrl, int trajcontrol, int B, int T) {
     Dims d;
