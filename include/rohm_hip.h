@@ -1064,6 +1064,53 @@ int rohm_floor_hypotheses(const float* points, int P, const float* joints, int N
 int rohm_floor_moments(const float* points, int P, const double* plane, const double* origin, double tau, double* out,
                        rohm_stream_t stream);
 
+/* SMPL-X from 3-D joints (csrc/fit.hip; rohm_amd/fit.py drives the two entry points, tests/fit_ref.py restates them).  No
+ * counterpart in the reference.  All arrays are device memory; the inputs are float32 where the project's forward
+ * kinematics takes float32, all arithmetic is float64; no atomics (the same input gives the same bits), no allocation, no
+ * synchronisation.
+ *
+ * rohm_fit_pose: one Levenberg-Marquardt problem per frame.  targets [N,22,3] float32 in SMPL joint order, any frame of
+ * reference; conf [N,22] float32 or NULL (ones); betas [N,10] float32; init, prev [N,69] float64 or NULL; w_prior [22]
+ * float64.  c_j = conf_j, or 0 for a target or confidence that is not finite or a confidence <= 0.  Unknowns x [69]: the
+ * axis-angles of joints 0..21, then the translation t.
+ *   E(x) = sum_j c_j |p_j + t - y_j|^2 + sum_k w_prior[k] |theta_k|^2 + w_smooth sum_{k=1..21} |theta_k - m_k|^2
+ * p_j: rohm_smplx_joints' joints (angle |r + 1e-8|, axis r / angle, rest joints Jt + Js beta, the forward chain) in float64.
+ * m_k: the mean of prev's theta_k over those of the frames i - 1, i + 1 that exist and whose whole prev row is finite; with
+ * prev NULL or no such neighbour the smoothing term is absent (the root, k = 0, is never smoothed).
+ * Jacobian: d p_j / d theta_k = -[p_j - p_k]x G_k J_r(theta_k) for k a strict ancestor of j (G_k the world rotation,
+ * J_r = I - (1 - cos a) / a^2 K + (a - sin a) / a^3 K^2 with K = [theta_k]x, a = |theta_k|; below a = 1e-6 the factors are
+ * 1/2 - a^2/24 and 1/6 - a^2/120), d / dt = I.  H = J^T C J + diag(w_prior + smoothing), g = J^T C r + w_prior theta +
+ * w_smooth (theta - m): half the gradient of E.
+ * Start: the init row when init is given and that row is finite.  Else theta = 0 but for the root, R_0 = F(y) F(rest)^T with
+ * F(v) = [x^ u^ z^], x^ = norm(v_1 - v_2), u^ = norm of the part of v_12 - (v_1 + v_2) / 2 orthogonal to x^, z^ = x^ x u^,
+ * turned into an axis-angle (c = (tr R - 1) / 2, v = (R21 - R12, R02 - R20, R10 - R01), s = |v| / 2, angle = atan2(s, c);
+ * v angle / (2 s) when s >= 1e-6 and c > -0.99, v / 2 when c > 0 otherwise, else the axis from the largest diagonal element
+ * of (R + R^T) / 2, signed to agree with v), and t = sum c (y - p) / sum c.
+ * report [N,6]: status, E at the start, E at the end, accepted iterations, the final lambda, sqrt(sum c |r|^2 / sum c).
+ * Status 0: fewer than min_joints joints have c > 0.  Status 2: no usable init row and joint 1, 2 or 12 has c = 0 or a norm
+ * of a triad (of the targets or of the rest joints) is below 1e-9.  Both give a zero params row, NaN for report 1, 2, 4, 5,
+ * 0 accepted and a zero normal block.  Status 1 otherwise.
+ * Iteration: lambda starts at 1e-3.  Each of the `iters` iterations builds H and g and makes up to 8 tries: solve
+ * (H + lambda diag(diag(H) + 1e-9)) d = -g by Cholesky (a pivot that is not positive is a rejected try); accept when
+ * E(x + d) < E(x), then lambda = max(lambda / 10, 1e-9) and the iteration ends; otherwise lambda = min(10 lambda, 1e8).
+ * Eight rejections leave x alone.  iters == 0 evaluates only: params is the start.  normal [N,69,70] (may be NULL) receives
+ * H (columns 0..68) and g (column 69) at the start.  params [N,69], report and normal are written wholly.
+ * One workgroup of 256 threads per frame, H (packed), the Jacobian and the Cholesky factor in 65 KiB of LDS.  N == 0
+ * returns without a launch. */
+int rohm_fit_pose(const rohm_smplx_t* h, const float* targets, const float* conf, const float* betas, const double* init,
+                  const double* prev, const double* w_prior, double w_smooth, int iters, int min_joints, int N,
+                  double* params, double* report, double* normal, rohm_stream_t stream);
+
+/* rohm_fit_shape_moments: with the pose fixed the joints are linear in the shape, p_j + t = a_j + A_j beta: A_0 = Js_0,
+ * A_j = A_parent + G_parent (Js_j - Js_parent) (Js [3,10] per joint: the handle's joint shape directions), a_j the same chain
+ * on Jt, plus t.  targets, conf as above; params [N,69] float64; use [N] uint8.  per_frame [N,66] float64, every row
+ * written (zeros where use == 0): the upper triangle of sum_j c_j A_j^T A_j (55 values, row-major, i <= j), sum_j c_j
+ * A_j^T (y_j - a_j) (10 values), sum_j c_j |y_j - a_j|^2.  out [66]: the sum of the rows in a fixed order (one workgroup
+ * per value: thread t takes the frames t, t + 256, ..., a xor-butterfly per wave, then the 4 wave partials in wave order).
+ * Two launches.  N == 0 returns without a launch and leaves out alone. */
+int rohm_fit_shape_moments(const rohm_smplx_t* h, const float* targets, const float* conf, const double* params,
+                           const unsigned char* use, int N, double* per_frame, double* out, rohm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

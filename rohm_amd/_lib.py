@@ -243,6 +243,8 @@ SIGNATURES = {
     'rohm_floor_hypotheses': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double] +
                               [C.c_void_p] * 4),
     'rohm_floor_moments': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    'rohm_fit_pose': (C.c_int, [C.c_void_p] * 7 + [C.c_double, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    'rohm_fit_shape_moments': (C.c_int, [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3),
 }
 
 
