@@ -18,6 +18,14 @@
  *     The training entry points (rohm_posenet_train_*, rohm_trajnet_train_*) have no handle: they read the
  *     caller's LIVE parameters in the reference's layouts on every call and keep their state in caller-owned
  *     `saved` / `scratch` buffers (*_saved_bytes, *_scratch_bytes).
+ *   - alignment: x_t, cond, noise, x, t, d_out and the outputs of rohm_posenet_forward / _sample_loop / _train_*,
+ *     rohm_ddpm_step[_table], rohm_q_sample and rohm_guidance_* need the alignment of their element only: they may be a batch
+ *     slice of a larger tensor (8 bytes past a 16-byte boundary for [B, 294, 1, 143]).  So do the LIVE parameter and gradient
+ *     pointers of rohm_posenet_train_* (views into a flat buffer): a kernel takes a 16-byte access through such a pointer only
+ *     where the address allows it.  tests/test_gpu_bounds.py runs these calls on batch slices and compares bit for bit.  Other
+ *     entry points state what they need (the GEMM building blocks' A / W, every `ws` / `scratch` / `saved`).
+ *   - a call reads and writes only the operands it is given, and of `ws` / `scratch` / `saved` only the first *_bytes bytes
+ *     (tests/test_gpu_bounds.py: guard bands around every buffer).
  *   - every launch goes on the caller-supplied hipStream_t (passed as void*);
  *     no hidden device synchronisation in forward / step / loop calls.  Set-up calls say so where they
  *     synchronise: *_create, rohm_exchange_probe, rohm_posenet_set_exchange(h, 1), the status read

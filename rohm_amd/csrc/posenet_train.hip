@@ -143,6 +143,13 @@ __global__ __launch_bounds__(256) void tgemm_kernel(TG p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- row kernels
+// Four floats of a caller's LIVE parameter (gamma, beta): the ABI asks only 4-byte alignment of a parameter (it may be a view into
+// a flat buffer), so the 16-byte load is taken only where the address allows it.  `saved` and `scratch` are 16-byte aligned by contract.
+__device__ __forceinline__ f32x4 param4(const float* p) {
+    if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) return *reinterpret_cast<const f32x4*>(p);
+    return f32x4{p[0], p[1], p[2], p[3]};
+}
+
 // LayerNorm over D = 512 (one wave per row, 8 columns per lane): y = (x - mu) rstd g + b, stats[row] = (mu, rstd).
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                      const float* __restrict__ b, float* __restrict__ y, float* __restrict__ stats,
@@ -159,8 +166,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 #pragma unroll
     for (int q = 0; q < 4; ++q) ss += (v0[q] - mu) * (v0[q] - mu) + (v1[q] - mu) * (v1[q] - mu);
     const float rstd = 1.0f / sqrtf(wave_sum64(ss) * (1.0f / kD) + eps);
-    const f32x4 g0 = *reinterpret_cast<const f32x4*>(g + 4 * lane), g1 = *reinterpret_cast<const f32x4*>(g + 256 + 4 * lane);
-    const f32x4 b0 = *reinterpret_cast<const f32x4*>(b + 4 * lane), b1 = *reinterpret_cast<const f32x4*>(b + 256 + 4 * lane);
+    const f32x4 g0 = param4(g + 4 * lane), g1 = param4(g + 256 + 4 * lane);
+    const f32x4 b0 = param4(b + 4 * lane), b1 = param4(b + 256 + 4 * lane);
     f32x4 o0, o1;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -188,7 +195,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
     for (int h = 0; h < 2; ++h) {
         const f32x4 xv = *reinterpret_cast<const f32x4*>(x + o + 256 * h + 4 * lane);
         const f32x4 dv = *reinterpret_cast<const f32x4*>(dy + o + 256 * h + 4 * lane);
-        const f32x4 gv = *reinterpret_cast<const f32x4*>(g + 256 * h + 4 * lane);
+        const f32x4 gv = param4(g + 256 * h + 4 * lane);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             xh[4 * h + q] = (xv[q] - mu) * rstd;

@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE ONLY (host side of tests/test_gpu_stale_memory.py): the memory-poisoning replacement of torch's
 uninitialised allocators, bit-exact comparison, the parser that lists every entry point of include/rohm_hip.h taking a
-caller-owned buffer, and the coverage list that names the case(s) exercising each of them.
+caller-owned buffer, and the coverage list that names the case(s) exercising each of them; for tests/test_gpu_bounds.py also the
+parser that lists every entry point with a pointer to numbers (`abi_pointer_functions`) and its exemptions.
 
 include/rohm_hip.h ("Caller-owned memory") promises that `ws`, `scratch`, `saved` and output buffers may hold anything on
 entry.  Every Python wrapper gets them from torch.empty / empty_like / new_empty; `poison` replaces those three for the
@@ -124,6 +125,44 @@ def abi_buffer_functions(text=None):
             out[m.group(1)] = names
     return out
 
+
+_POINTEE = r'(?:float|double|void|int|unsigned(?:\s+(?:char|int))?|long\s+long|size_t|u?int(?:8|16|32|64)_t)'
+
+
+def abi_pointer_functions(text=None):
+    """{entry point: [parameter names]} for every declaration of include/rohm_hip.h with a parameter that points at numbers --
+    `float*`, `double*`, `void*`, an integer pointer, a table of such pointers (`float* const*`), const or not: every function that
+    can be handed a caller's tensor.  Pointers to structs, handles and strings are not listed.  The header does not say in its types
+    which of these live on the host (plans, limits, camera matrices): POINTER_EXEMPT names the host-only calls one by one, and
+    tests/test_guarded_memory_host.py holds every other function to a guarded-memory case."""
+    if text is None:
+        with open(HEADER) as f:
+            text = f.read()
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'//[^\n]*', ' ', text)
+    out = {}
+    for m in re.finditer(r'\b(rohm_\w+)\s*\(([^;{}()]*)\)\s*;', text):
+        names = []
+        for param in m.group(2).split(','):
+            p = re.match(r'^\s*(?:const\s+)?' + _POINTEE + r'\s*(?:const\s*)?\*\s*(?:const\s*\*\s*)?(?:const\s+)?(\w+)\s*$', param)
+            if p:
+                names.append(p.group(1))
+        if names:
+            out[m.group(1)] = names
+    return out
+
+
+# entry points with a pointer parameter that no guarded-memory case runs (tests/test_gpu_bounds.py), each with its reason
+POINTER_EXEMPT = {
+    'rohm_profile_stop': 'host-only: the row count goes to a host int, nothing on the device is touched',
+    'rohm_output_process_plan': 'host-only: the launch plan is returned through two host ints',
+    'rohm_adamw_limits': 'host-only: two host ints',
+    'rohm_smplx_create': 'create: copies the model arrays into device memory the handle owns, sized by V, J and n_shape_total',
+    'rohm_smplx_set_skinning': 'create-time upload of the skinning arrays into memory the handle owns',
+    'rohm_posenet_exchange_status': 'status call: reads the exchange header of a workspace a forward of the same shape wrote; it is run '
+                                    'after every PoseNet case as check_exchange',
+    'rohm_posenet_set_stack_timeline': 'timeline call: registers a diagnostic output buffer; tests/test_gpu_chain.py checks its size',
+}
 
 # entry points that take a buffer but are not run by a case, each with its reason (at most these two: a third needs a sentence in the
 # pull request that adds it saying why the contract does not apply)
