@@ -33,6 +33,7 @@
  *     probe an un-probed device on their FIRST call unless the stream records a graph (see there).
  *     One loop call does wait: rohm_trajnet_sample_loop in its clip-resident form (TrajNet's default, see rohm_trajnet_loop_mode)
  *     synchronises `stream` once at its end to read the in-kernel meetings' error word (ROHM_TRAJ_RESIDENT=0 keeps it wait-free).
+ *     tests/test_gpu_stream_order.py holds every entry point to this (inputs that arrive late on a side stream, a call log).
  *   - handles are immutable after create (documented exceptions, all control calls that must not race with
  *     launches of the same handle: rohm_posenet_set_exchange, rohm_posenet_inject_exchange_fault,
  *     rohm_posenet_set_stack_timeline); calls are re-entrant across streams given distinct workspaces.
