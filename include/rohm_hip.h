@@ -34,6 +34,35 @@
  *     One loop call does wait: rohm_trajnet_sample_loop in its clip-resident form (TrajNet's default, see rohm_trajnet_loop_mode)
  *     synchronises `stream` once at its end to read the in-kernel meetings' error word (ROHM_TRAJ_RESIDENT=0 keeps it wait-free).
  *     tests/test_gpu_stream_order.py holds every entry point to this (inputs that arrive late on a side stream, a call log).
+ *   - recordable calls: every entry point that takes a rohm_stream_t and is not named below as waiting may be called on a stream
+ *     that records a hipGraph.  A replay does exactly what the recorded call would do if it were made again with the same argument
+ *     values: device operands are read at replay time; host scalars (step, seed, coefficients, sizes) and host arrays (t_model,
+ *     coef, pointer and numel tables, camera matrices, rohm_result_rows_item lists) are read at the call and travel in the kernel
+ *     arguments, so the caller may rewrite or free host arrays as soon as the call returns -- no recorded node points at caller host
+ *     memory.  A replay therefore repeats the recorded `step` of rohm_adamw_step and the recorded `seed` of
+ *     rohm_posenet_train_forward: a caller that wants them to move records one graph per value or passes them through device
+ *     memory of its own design (rohm_amd.optim.AdamW.step() and PoseNet.forward in train mode with dropout > 0 raise while the
+ *     current stream records, because they would freeze them silently).  Process-wide read-outs describe the recording call, not
+ *     the replays: rohm_trajnet_loop_mode, rohm_trajnet_train_last_gemms, rohm_last_error.
+ *     Waiting calls cannot be recorded.  rohm_track_resample waits for its stream to check valid_idx on the host and is refused
+ *     on a recording stream.  rohm_floor_hypotheses waits for its stream to check the triples on the host and is refused on a
+ *     recording stream.  rohm_posenet_exchange_status waits for its stream to read the status word and is refused on a recording
+ *     stream.  Refused means: the call returns ROHM_ERR_UNSUPPORTED with a rohm_last_error that names the function, before it issues
+ *     or synchronises anything, so the caller's capture stays valid.  rohm_trajnet_sample_loop steps aside instead: on a recording
+ *     stream it takes its launch-per-layer form, which does not wait (rohm_trajnet_loop_mode() reports 0 for that call).
+ *     Warm-up: none is required for correctness.  Two first-call decisions are taken differently while recording, neither changes
+ *     a result: on a device that has not been probed (rohm_exchange_probe) rohm_gemm_res_layernorm_f32 refuses and
+ *     rohm_output_process_f32 uses plain tiles (see there); and a host thread whose FIRST TrajControl loop call is recorded gets
+ *     the one-stream order in that graph, because the control stream and its events are not created under a capture -- one eager
+ *     rohm_trajnet_sample_loop call on that thread before the capture gives the graph its parallel branch (bit-identical either
+ *     way; that branch needs the runtime's default of four hardware queues to replay).  The Python wrappers allocate workspaces
+ *     per call or cache them per handle and shape: under torch.cuda.graph an allocation made while recording belongs to the graph's
+ *     pool, so call a wrapper once eagerly first, as torch asks for any captured code.
+ *     The launch profiler (rohm_profile_start) is outside this contract: it records events of its own around every launch; record
+ *     with it off.
+ *     tests/test_gpu_graph_replay.py records every such entry point on one set of values, replays it over poisoned outputs and
+ *     workspaces on a second set and on the first again, with the host arrays it can reach rewritten after the capture, and
+ *     compares bit for bit with eager calls; the three waiting calls are refused there with the capture left valid.
  *   - handles are immutable after create (documented exceptions, all control calls that must not race with
  *     launches of the same handle: rohm_posenet_set_exchange, rohm_posenet_inject_exchange_fault,
  *     rohm_posenet_set_stack_timeline); calls are re-entrant across streams given distinct workspaces.

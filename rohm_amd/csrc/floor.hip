@@ -317,7 +317,13 @@ extern "C" int rohm_floor_hypotheses(const float* points, int P, const float* jo
     ROHM_ARG_CHECK(P >= 3, "floor_hypotheses: a plane needs 3 points, got P=%d with K=%d", P, K);
     ROHM_ARG_CHECK(points && triples && planes && scores && best && (joints || NJ == 0), "floor_hypotheses: null argument");
     ROHM_ARG_CHECK((long long)P * 3 <= INT_MAX && (long long)NJ * 3 <= INT_MAX, "floor_hypotheses: P=%d or NJ=%d is more than one launch takes", P, NJ);
-    // the triples are the host's (K x 3 integers): read them back once and check them, the kernel indexes with them
+    // the triples are the host's (K x 3 integers): read them back once and check them, the kernel indexes with them.  That read waits
+    // for the stream, and a wait on a recording stream invalidates the caller's capture: refuse before anything is issued.
+    if (stream_is_capturing((hipStream_t)stream)) {
+        set_error("rohm_floor_hypotheses waits for its stream (it checks the triples on the host) and cannot be recorded into a graph: call "
+                  "it outside the capture");
+        return ROHM_ERR_UNSUPPORTED;
+    }
     std::vector<int> tr((size_t)K * 3);
     ROHM_HIP_CHECK(hipMemcpyAsync(tr.data(), triples, sizeof(int) * tr.size(), hipMemcpyDeviceToHost, (hipStream_t)stream));
     ROHM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));

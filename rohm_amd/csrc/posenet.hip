@@ -1011,6 +1011,12 @@ int rohm_posenet_exchange_status(const rohm_posenet_t* h, int B, int T, void* ws
     Workspace w = carve(h, B, T, (float*)ws);
     ROHM_ARG_CHECK(w.floats * sizeof(float) <= ws_bytes, "posenet_exchange_status: workspace too small");
     hipStream_t s = (hipStream_t)stream;
+    // a wait on a recording stream invalidates the caller's capture: refuse before anything is issued
+    if (stream_is_capturing(s)) {
+        set_error("rohm_posenet_exchange_status waits for its stream (it reads the status word on the host) and cannot be recorded into a "
+                  "graph: call it after the replay");
+        return ROHM_ERR_UNSUPPORTED;
+    }
     unsigned st[2] = {0u, 0u};
     ROHM_HIP_CHECK(hipMemcpyAsync(st, w.xln, sizeof(st), hipMemcpyDeviceToHost, s));
     ROHM_HIP_CHECK(hipStreamSynchronize(s));

@@ -131,7 +131,13 @@ extern "C" int rohm_track_resample(const double* times_src, const int* valid_idx
     ROHM_ARG_CHECK(M == 0 || (mask_joint && mask_out), "track_resample: M = %d needs mask_joint and mask_out", M);
     const long long total = (long long)n_out * (kTrackFixedSlots + J + M);
     ROHM_ARG_CHECK((total + 255) / 256 <= 0x7fffffffLL, "track_resample: %lld slots are more than one launch takes", total);
-    // the valid list is the host's (a few thousand integers): read it back once and check it, the kernel indexes with it
+    // the valid list is the host's (a few thousand integers): read it back once and check it, the kernel indexes with it.  That read
+    // waits for the stream, and a wait on a recording stream invalidates the caller's capture: refuse before anything is issued.
+    if (stream_is_capturing((hipStream_t)stream)) {
+        set_error("rohm_track_resample waits for its stream (it checks valid_idx on the host) and cannot be recorded into a graph: call it "
+                  "outside the capture");
+        return ROHM_ERR_UNSUPPORTED;
+    }
     std::vector<int> vi((size_t)Nv);
     ROHM_HIP_CHECK(hipMemcpyAsync(vi.data(), valid_idx, sizeof(int) * (size_t)Nv, hipMemcpyDeviceToHost, (hipStream_t)stream));
     ROHM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));

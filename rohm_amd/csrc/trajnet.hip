@@ -34,15 +34,12 @@ __global__ __launch_bounds__(256) void pad_rows_kernel(const float* __restrict__
 // Timestep path of one step: SinusoidalPosEmb(32) -> Linear(32,128) -> Mish -> Linear(128,32)
 // (trajnet.py:120-125, heads.py:57-69), then every block's `Mish -> Linear(32, C_out)` (heads.py:34-38)
 // stacked into one [tb_total] vector.  One block per row (sample, or 1 when the batch shares t).
-__global__ __launch_bounds__(256) void time_path_kernel(const int64_t* __restrict__ t_dev, int64_t t_host, int tdim,
-                                                        const float* __restrict__ w1T, const float* __restrict__ b1,
-                                                        const float* __restrict__ w3T, const float* __restrict__ b3,
-                                                        const float* __restrict__ tbwT, const float* __restrict__ tbb,
-                                                        int tb_total, float* __restrict__ tb_all) {
+__device__ __forceinline__ void time_path_row(float tval, int tdim, const float* __restrict__ w1T, const float* __restrict__ b1,
+                                              const float* __restrict__ w3T, const float* __restrict__ b3,
+                                              const float* __restrict__ tbwT, const float* __restrict__ tbb, int tb_total,
+                                              float* __restrict__ tb_all) {
     __shared__ float e[64], h[256], te[64];
     const int tid = threadIdx.x;
-    // t: per sample (t_dev) or shared by the batch (t_host)
-    const float tval = (float)(t_dev ? t_dev[blockIdx.x] : t_host);
     const int half = tdim / 2;
     if (tid < tdim) {
         const int k = tid % half;
@@ -68,6 +65,27 @@ __global__ __launch_bounds__(256) void time_path_kernel(const int64_t* __restric
         for (int k = 0; k < tdim; ++k) a = fmaf(te[k], tbwT[(size_t)k * tb_total + o], a);
         tb_all[(size_t)blockIdx.x * tb_total + o] = a;
     }
+}
+
+__global__ __launch_bounds__(256) void time_path_kernel(const int64_t* __restrict__ t_dev, int64_t t_host, int tdim,
+                                                        const float* __restrict__ w1T, const float* __restrict__ b1,
+                                                        const float* __restrict__ w3T, const float* __restrict__ b3,
+                                                        const float* __restrict__ tbwT, const float* __restrict__ tbb,
+                                                        int tb_total, float* __restrict__ tb_all) {
+    // t: per sample (t_dev) or shared by the batch (t_host)
+    time_path_row((float)(t_dev ? t_dev[blockIdx.x] : t_host), tdim, w1T, b1, w3T, b3, tbwT, tbb, tb_total, tb_all);
+}
+
+// The timesteps of a run of loop steps, one block per step.  They travel BY VALUE, in the kernel's arguments: the caller's host array
+// is read at the call and never again, so a launch recorded into a graph replays the recorded timesteps whatever has become of that
+// array (a recorded host-to-device copy would read it again at every replay), and there is no upload at all.
+struct StepTimes { int64_t t[kTbSteps]; };
+__global__ __launch_bounds__(256) void time_path_steps_kernel(StepTimes ts, int tdim,
+                                                              const float* __restrict__ w1T, const float* __restrict__ b1,
+                                                              const float* __restrict__ w3T, const float* __restrict__ b3,
+                                                              const float* __restrict__ tbwT, const float* __restrict__ tbb,
+                                                              int tb_total, float* __restrict__ tb_all) {
+    time_path_row((float)ts.t[blockIdx.x], tdim, w1T, b1, w3T, b3, tbwT, tbb, tb_total, tb_all);
 }
 
 // Fused GroupNorm(8 groups, eps 1e-5, biased variance over (C/8 x T) per sample) -> Mish -> (+ time bias)
@@ -590,7 +608,6 @@ static TWs carve_t(const rohm_trajnet* h, int B, int T, float* base) {
         w.splitk_ctl = take(kSplitKFloats);
         w.splitk_res_ctl = take(kSplitKFloats);
     }
-    w.step_t = reinterpret_cast<int64_t*>(take(2 * (size_t)kTbSteps));
     w.resident = take(resident_floats(B, T));
     w.floats = off;
     return w;
@@ -752,9 +769,11 @@ static int run_time_path(const rohm_trajnet* h, const TWs& w, const int64_t* t_d
 
 // the time path depends on t only (trajnet.py:120-125, heads.py:35-38): one launch covers a run of loop steps (37 us per step before)
 int launch_time_path_steps(const rohm_trajnet* h, const TWs& w, const int64_t* t, int run, hipStream_t s) {
-    ROHM_HIP_CHECK(hipMemcpyAsync(w.step_t, t, (size_t)run * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    ROHM_ARG_CHECK(run >= 1 && run <= kTbSteps, "trajnet: a run of %d loop steps does not fit one time-path launch", run);
+    StepTimes ts{};
+    for (int i = 0; i < run; ++i) ts.t[i] = t[i];
     prof::Scope ps("time_path", 0.0, 4.0 * h->tb_total * h->tdim * run, s);
-    hipLaunchKernelGGL(time_path_kernel, dim3(run), dim3(256), 0, s, w.step_t, (int64_t)0, h->tdim, h->t_w1T, h->t_b1, h->t_w3T,
+    hipLaunchKernelGGL(time_path_steps_kernel, dim3(run), dim3(256), 0, s, ts, h->tdim, h->t_w1T, h->t_b1, h->t_w3T,
                        h->t_b3, h->tb_wT, h->tb_b, h->tb_total, w.tb_steps);
     ROHM_LAUNCH_CHECK();
     return ROHM_OK;
@@ -792,12 +811,15 @@ struct SideStream {
     hipEvent_t ev_in = nullptr, ev_ctl[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
     int device = -1;
 };
-static SideStream* side_stream(int device) {
+static SideStream* side_stream(int device, hipStream_t caller) {
     const char* e = getenv("ROHM_TRAJ_CTRL_STREAM");      // read per loop call (once per 100 steps): tests flip it
     if (e && e[0] == '0') return nullptr;
     static thread_local SideStream ss;
     if (ss.s2 && ss.device == device) return &ss;
     if (ss.s2) return nullptr;                  // a host thread that drives two devices keeps the one-stream order on the second
+    // no stream or event is created while the caller records a graph: a thread whose first loop call is recorded keeps the one-stream
+    // order for that graph (bit-identical; an eager loop call before the capture gives the graph its parallel branch)
+    if (stream_is_capturing(caller)) return nullptr;
     if (hipStreamCreateWithFlags(&ss.s2, hipStreamNonBlocking) != hipSuccess) { ss.s2 = nullptr; (void)hipGetLastError(); return nullptr; }
     bool ok = hipEventCreateWithFlags(&ss.ev_in, hipEventDisableTiming) == hipSuccess;
     for (int i = 0; i < 2 && ok; ++i)
@@ -1148,7 +1170,7 @@ int rohm_trajnet_sample_loop(const rohm_trajnet_t* h, float* x, const float* con
         if (rc != ROHM_ERR_UNSUPPORTED) return rc;
         if ((rc = pad_rows(x, w.xin, M, h->ctraj, kPadC, s))) return rc;
     }
-    SideStream* ss = h->control ? side_stream(h->device) : nullptr;
+    SideStream* ss = h->control ? side_stream(h->device, s) : nullptr;
     if (ss && !control_pre_done && (rc = run_control_pre(h, w, B, T, s))) return rc;           // control_zero_conv_0(control_cond): once per loop
     // an early return must not leave side-stream work behind that still reads / writes the caller-owned workspace un-ordered
     // against the caller's stream: join s2 into s first

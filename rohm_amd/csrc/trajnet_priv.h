@@ -91,7 +91,6 @@ struct TWs {
     Scratch sc;
     float *x0, *cond_keep;                  // loop: network output [B,T,13]
     float *splitk, *splitk_res;             // split-K partial tiles (plan_split)
-    int64_t* step_t;                        // [kTbSteps]: timesteps of a run of loop steps (launch_time_path_steps)
     float* resident;                        // clip-resident sample loop: layer list, meeting flags, statistics slots, x_T (trajnet_resident.hip)
     size_t floats;
 };

@@ -422,8 +422,16 @@ class PoseNet(nn.Module):
 
     def _forward_train(self, x_t, cond, timesteps, params):
         """Train-mode forward through `_PoseNetTrain`: dropout self.dropout at the reference's five sites, the seed drawn from
-        torch's CPU generator (torch.manual_seed reproduces a step); kept in `last_dropout_seed` for diagnostics."""
+        torch's CPU generator (torch.manual_seed reproduces a step); kept in `last_dropout_seed` for diagnostics.  That seed is a
+        host scalar of rohm_posenet_train_forward: recorded into a graph, every replay would repeat the same masks, so with
+        dropout > 0 the call is refused while the current stream records (with dropout 0 it records)."""
         p = float(self.dropout)
+        if p > 0:
+            with torch.cuda.device(x_t.device):
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError('PoseNet.forward in train mode with dropout > 0 cannot be recorded into a graph: the dropout seed is '
+                                       'drawn on the host, and every replay would repeat the same masks.  Record '
+                                       'rohm_posenet_train_forward yourself with the seed you mean to replay, or train with dropout 0.')
         seed = int(torch.randint(0, 2 ** 62, (), dtype=torch.int64).item()) if p > 0 else 0
         self.last_dropout_seed = seed
         return _PoseNetTrain.apply(self, x_t, cond, timesteps, p, seed, *params)

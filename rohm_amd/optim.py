@@ -16,6 +16,10 @@ implementations and are ignored here: the step is always the one fused multi-ten
 the host step counters (inside, the counters of the parameters that step together are views of one host tensor, and torch's
 `load_state_dict` keeps a host `step` tensor as it is, so a live native state dict would otherwise share them with its loader).
 
+`step()` raises while the current stream records a graph: the step count is a host scalar of `rohm_adamw_step`, and a graph would
+repeat the recorded count -- its bias correction -- at every replay while the counters here stand still (torch's non-capturable
+AdamW raises there too).  The entry point itself records (include/rohm_hip.h, "recordable calls").
+
 There is no eager fallback: parameters must be contiguous fp32 tensors on a HIP device with dense gradients.
 """
 from __future__ import annotations
@@ -154,8 +158,24 @@ class AdamW(torch.optim.Optimizer):
             st['step'] = view
         return values
 
+    def _refuse_while_recording(self):
+        """Raise while the current stream records a graph, before the closure runs, any state is created or anything is issued: the
+        step count is a host scalar of rohm_adamw_step, a graph would hold this call's value, and every replay would repeat its bias
+        correction while the counters here stand still (torch's non-capturable AdamW raises there too)."""
+        device = getattr(self, '_device', None)
+        if device is None:
+            return
+        with torch.cuda.device(device):
+            if not torch.cuda.is_current_stream_capturing():
+                return
+        counts = [int(st['step']) for st in self.state.values() if 'step' in st]      # (read only: no state is created here)
+        raise RuntimeError(f'rohm_amd.optim.AdamW.step() cannot be recorded into a graph: the step count is a host scalar, and every '
+                           f'replay would repeat the frozen step count {max(counts, default=0) + 1}.  Step outside the capture, or '
+                           f'record rohm_adamw_step yourself with the step you mean to replay.')
+
     @torch.no_grad()
     def step(self, closure=None):
+        self._refuse_while_recording()
         loss = None
         if closure is not None:
             with torch.enable_grad():

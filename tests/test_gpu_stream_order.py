@@ -51,7 +51,7 @@ What stays unseen -- nobody should take it for covered:
     build from numpy arrays or host lists, tensors a case derives on the device, the weights of the inference handles); they are
     uploaded with a wait or computed in stream order, so they are simply ready;
   * anything after a documented wait inside the same call;
-  * graph capture of the entry points other than PoseNet's forward (tests/test_gpu_posenet.py): out of scope here;
+  * graph capture of the entry points: out of scope here, tests/test_gpu_graph_replay.py records and replays every one of them;
   * device tensors among the recorded inputs (the training parameters) are matched by shape and dtype, not by value.
 
 Findings: nothing found.  Read before run, every launch, memset, copy, allocation and wait of rohm_amd/csrc: 147 kernel launch
@@ -66,9 +66,11 @@ caller's stream after the time table of each run of steps -- at step 0 that is a
 input, the only things the branch reads besides weights -- so it never reads a caller's tensor directly; the caller's stream waits
 for the branch's event before mid_blk[1], the first consumer; `s2` waits for the "consumed" event of step i - 2 before it reuses a
 set of residual buffers; an early return joins `s2` into the caller's stream.  The six TrajControl `resident 0` cases confirm it.
-The loops' step table comes from pageable host memory (hipMemcpyAsync, host to device, on the caller's stream): the call returns
-with the gate closed and the results are bit-equal although the wrapper's array is gone by then, i.e. the runtime stages it at the
-call.  No wrapper of rohm_amd/ passes anything but torch's current stream.
+The loops' step table came from pageable host memory when this was read (hipMemcpyAsync, host to device, on the caller's stream:
+one of the 11): the call returned with the gate closed and the results were bit-equal although the wrapper's array was gone by
+then, i.e. eagerly the runtime stages it at the call.  Recorded into a graph it does not (tests/test_gpu_graph_replay.py), so the
+timesteps travel in the kernel arguments since, and 10 hipMemcpyAsync are left.  No wrapper of rohm_amd/ passes anything but
+torch's current stream.
 
 Numbers (MI355X).  Gate length: the slowest host side of a single entry point in the plain runs is rohm_trajnet_train_backward,
 1.54 ms (TrajControl; 1.33 ms TrajNet), then rohm_trajnet_sample_loop launch per layer 0.63 - 1.10 ms, rohm_trajnet_forward
