@@ -247,6 +247,13 @@ SIGNATURES = {
     'rohm_fit_shape_moments': (C.c_int, [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3),
 }
 
+# the same for include/rohm_multiview.h
+SIGNATURES_MULTIVIEW = {
+    'rohm_mv_limits': (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'rohm_mv_triangulate': (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_double] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 6),
+    'rohm_mv_residuals': (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_double, C.c_void_p, C.c_void_p]),
+}
+
 
 def lib():
     """Load (once) and return the ctypes library; raises if it has not been built."""
@@ -260,7 +267,7 @@ def lib():
         # the shipped library must export every declared symbol; an experiment library selected through ROHM_HIP_LIB (same-box A/B
         # runs against an older tree, scripts/build_variant.py) may lack the newest ones -- they then fail where they are used
         strict = not os.environ.get('ROHM_HIP_LIB')
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_MULTIVIEW.items()):
             if not strict and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)
