@@ -254,6 +254,11 @@ SIGNATURES_MULTIVIEW = {
     'rohm_mv_residuals': (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_double, C.c_void_p, C.c_void_p]),
 }
 
+# the same for include/rohm_fit_views.h
+SIGNATURES_FIT_VIEWS = {
+    'rohm_fit_views_pose': (C.c_int, [C.c_void_p] * 7 + [C.c_double] * 4 + [C.c_int] * 4 + [C.c_void_p] * 5),
+}
+
 
 def lib():
     """Load (once) and return the ctypes library; raises if it has not been built."""
@@ -267,7 +272,7 @@ def lib():
         # the shipped library must export every declared symbol; an experiment library selected through ROHM_HIP_LIB (same-box A/B
         # runs against an older tree, scripts/build_variant.py) may lack the newest ones -- they then fail where they are used
         strict = not os.environ.get('ROHM_HIP_LIB')
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_MULTIVIEW.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_MULTIVIEW.items()) + list(SIGNATURES_FIT_VIEWS.items()):
             if not strict and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)

@@ -158,12 +158,13 @@ def _views_dict(views):
     return dict(views)
 
 
-def read_views(views):
+def read_views(views, min_views=2):
     """Validate a views file (an .npz path or a dict) -> a dict with keypoints [V,N,K,3] float32 (K 22 or 25), camera_mtx
     [V,3,3], world2cam [V,4,4] (the inverse of cam2world where that was given), dist_coeffs [V,5] or None, world_up_axis 'z' |
     'y' | None, floor_height or None, and `time_key` ('fps' or 'times') with its value as given, frame_names and recording_name
     where given.  Required: keypoints_2d, camera_mtx, exactly one of world2cam and cam2world, exactly one of fps and times.  Any
-    key outside `VIEW_KEYS` is refused by name."""
+    key outside `VIEW_KEYS` is refused by name.  `min_views`: the fewest views accepted (triangulation needs two; `rohm_amd.fit_views`
+    reads a file with one)."""
     d = _views_dict(views)
     unknown = sorted(set(d) - set(VIEW_KEYS))
     if unknown:
@@ -175,8 +176,8 @@ def read_views(views):
     if kp.ndim != 4 or kp.shape[1] < 1 or kp.shape[2:] not in ((22, 3), (25, 3)):
         raise ValueError(f'views: keypoints_2d must be [V,N,22,3] (SMPL order) or [V,N,25,3] (BODY_25) with N >= 1, got {kp.shape}')
     V, N = kp.shape[:2]
-    if not 2 <= V <= 16:
-        raise ValueError(f'views: the number of views must be in [2, 16], got {V}')
+    if not min_views <= V <= 16:                                              # triangulation needs two; rohm_amd.fit_views reads one
+        raise ValueError(f'views: the number of views must be in [{min_views}, 16], got {V}')
     if ('world2cam' in d) == ('cam2world' in d):
         raise ValueError('views: give exactly one of world2cam and cam2world')
     key = 'world2cam' if 'world2cam' in d else 'cam2world'
