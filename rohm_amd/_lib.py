@@ -324,6 +324,33 @@ def require_hip(*tensors):
                                'got a CPU tensor and there is deliberately no CPU fallback')
 
 
+def hip_tensor(x, name, kernels):
+    """x, if it is a torch tensor on a HIP device; `kernels` is the caller's phrase for who asks ('the fit kernels take')."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f'{name}: {kernels} torch tensors on a HIP device, got {type(x).__name__}')
+    require_hip(x)
+    return x
+
+
+def hip_rows(x, name, shape, kernels):
+    """x (None stays None) as a contiguous float64 HIP tensor of exactly `shape`."""
+    if x is None:
+        return None
+    x = hip_tensor(x, name, kernels).detach().double().contiguous()
+    if tuple(x.shape) != tuple(shape):
+        raise ValueError(f'{name} must be {list(shape)}, got {list(x.shape)}')
+    return x
+
+
+def npz_dict(source):
+    """The arrays of an .npz path (no pickles), or a copy of a mapping."""
+    if isinstance(source, (str, os.PathLike)):
+        import numpy as np
+        with np.load(source, allow_pickle=False) as f:
+            return {k: f[k] for k in f.files}
+    return dict(source)
+
+
 def profile_start(step_stride=1):
     check(lib().rohm_profile_start(step_stride), 'rohm_profile_start')
 

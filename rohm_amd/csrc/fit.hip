@@ -3,8 +3,11 @@
 // the rules in full.  There is no counterpart in the reference: its recordings come with fitted parameters.
 //
 // All arithmetic is float64 on the float32 inputs, as in floor.hip.  No atomics, every sum is taken by one thread in a fixed
-// order or by a fixed butterfly: the same input gives the same bits.  The float32 helpers of smplx_fk.h cannot serve a float64
-// solver; their float64 siblings (the same Rodrigues convention, the same chain) are in fit_math.h.
+// order or by a fixed butterfly: the same input gives the same bits.  The float64 helpers, the Jacobian, the Cholesky solve, the
+// `normal` dump and the unfitted exit are fit_math.h's, shared with fit_views.hip.  The prologue, the smoothing set-up and the
+// Levenberg-Marquardt loop are written out here although fit_math.h has them for fit_views.hip (fit_lm and its pieces): with
+// 256 registers and spills this kernel is at the edge, and every way of taking them from there moved it off its instruction
+// stream and cost 0.7 to 2.6 % (profiles/fit_core_resources.md).  A rule changed there is changed here too.
 //
 // rohm_fit_pose: one workgroup of 256 threads per frame.  In LDS, as float64: the normal matrix H as a packed lower triangle
 // (2415 values, 19 KiB), the Jacobian of the 66 joint coordinates against the 66 rotation unknowns (34 KiB; the translation's
@@ -14,7 +17,7 @@
 // 22 lanes, the kinematic chain is serial on lane 0 (21 small products), and the lanes go to J^T C J (2415 dot products of 66
 // terms per iteration) and to the factorisation (69 steps, two barriers each; the triangular solves take one barrier per
 // step).
-#include "fit_math.h"                                // the float64 helpers, the Jacobian and the Cholesky solve, shared with fit_views.hip
+#include "fit_math.h"
 
 #include <limits.h>
 
@@ -160,7 +163,6 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(2))
     __shared__ FitShared s;
     const int tid = threadIdx.x;
     const size_t f = blockIdx.x;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
     double* params = a.params + f * kFitX;
     double* report = a.report + f * 6;
     double* normal = a.normal ? a.normal + f * kFitX * (kFitX + 1) : nullptr;
@@ -232,12 +234,7 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(2))
     __syncthreads();
     const int status = s.status;
     if (status != 1) {                               // skipped, or needs a start: zeros and NaN energies; the whole block leaves
-        for (int i = tid; i < kFitX; i += kFitThreads) params[i] = 0.0;
-        if (normal)
-            for (int i = tid; i < kFitX * (kFitX + 1); i += kFitThreads) normal[i] = 0.0;
-        if (tid == 0) {
-            report[0] = (double)status; report[1] = nan; report[2] = nan; report[3] = 0.0; report[4] = nan; report[5] = nan;
-        }
+        fit_unfitted(status, params, report, normal, tid);
         return;
     }
     bool from_init = a.init != nullptr;              // (uniform: every thread reads the same row)
@@ -265,12 +262,7 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(2))
         fit_normal(s, tid);
         fresh = true;
     }
-    if (normal) {
-        for (int e = tid; e < kFitX * (kFitX + 1); e += kFitThreads) {
-            const int i = e / (kFitX + 1), j = e % (kFitX + 1);
-            normal[e] = j == kFitX ? s.g[i] : s.H[i >= j ? tri(i, j) : tri(j, i)];
-        }
-    }
+    if (normal) fit_dump_normal(s, normal, tid);
     for (int it = 0; it < a.iters; ++it) {
         if (!fresh) {
             E = fit_evaluate<true>(s, s.x, tid);

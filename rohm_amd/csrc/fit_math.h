@@ -1,10 +1,15 @@
-// The float64 pieces that the Levenberg-Marquardt kernels of fit.hip (SMPL-X from 3-D joints) and fit_views.hip (SMPL-X from 2-D
-// keypoints) share: Rodrigues and the right Jacobian of SO(3), the logarithm, the kinematic chain, the Jacobian of the 66 joint
-// coordinates against the 66 rotation unknowns, and the damped Cholesky solve.  The float32 helpers of smplx_fk.h cannot serve a
-// float64 solver; these are their float64 siblings (the same Rodrigues convention, the same chain).  Private to csrc.
+// The float64 pieces of the Levenberg-Marquardt kernels of fit.hip (SMPL-X from 3-D joints) and fit_views.hip (SMPL-X from 2-D
+// keypoints).  Both use: Rodrigues, the right Jacobian of SO(3), the logarithm and the kinematic chain (the siblings of smplx_fk.h's
+// float32 helpers: the same Rodrigues convention, the same chain), the Jacobian of the 66 joint coordinates against the 66
+// rotation unknowns, the damped Cholesky solve, the `normal` dump and the "not fitted" exit.  The rest is the solver as
+// fit_views.hip runs it, everything but a data term: the LDS it keeps (FitCore), the prologue pieces, the prior and smoothing
+// part of the energy and of the gradient, the walk over the packed triangle of H and the iteration itself (fit_lm).  fit.hip
+// still writes those out for itself (its header says why); a solver to come takes them from here.  Private to csrc.
 //
-// The two templates take the kernel's LDS struct S.  fit_jacobian needs G, M, P [NJ x 9 / 9 / 3], anc [NJ] and W [66 x 66];
-// fit_solve needs H (packed lower triangle), W (at least kFitTri values), g, dg, rhs, sol [69].
+// The templates take the kernel's LDS struct S (fit_jacobian, fit_solve, fit_dump_normal: any struct with the members they name;
+// the others: one that extends FitCore).  A kernel hands fit_lm a "problem" p: p.evaluate<kJac>(x) is the energy at x, the same
+// value in every thread, behind a barrier (kJac also leaves J_r in M and whatever the next two need); p.hessian(i, j) and
+// p.gradient(i) are the data term's share of H and g at s.x.
 #pragma once
 #include "smplx_fk.h"
 
@@ -102,6 +107,106 @@ __device__ __forceinline__ void chain64(const double* R, const double* rest, con
     }
 }
 
+// What a solver keeps in LDS whatever its data term; FitViewsShared (fit_views.hip) extends it with its data term's members.
+struct FitCore {
+    double H[kFitTri];            // packed lower triangle
+    double W[kFitRot * kFitRot];  // the Jacobian [66 rows][66 columns]; then the packed Cholesky factor (strictly lower part)
+    double g[kFitX], dg[kFitX], rhs[kFitX], sol[kFitX];
+    double x[kFitX], xt[kFitX];
+    double R[NJ * 9], G[NJ * 9], M[NJ * 9];          // local and world rotations; M = G J_r
+    double P[NJ * 3], rest[NJ * 3];
+    double mean[kFitX], wdiag[kFitX], wsm[kFitX], wp[NJ];    // (the translation's three entries carry the smoothing only)
+    double E;
+    int parents[NJ];
+    unsigned anc[NJ];             // bit k: joint k is a strict ancestor
+    int status;
+};
+
+// prologue, all lanes: parents and prior weights on 22 lanes, the rest joints Jt + Js betas on 66.  The caller's barrier follows.
+template <class S>
+__device__ __forceinline__ void fit_load_body(S& s, const float* __restrict__ Jt, const float* __restrict__ Js, const int* __restrict__ parents,
+                                              const float* __restrict__ betas, const double* __restrict__ w_prior, int tid) {
+    if (tid < NJ) {
+        s.parents[tid] = parents[tid];
+        s.wp[tid] = w_prior[tid];
+    }
+    if (tid < kFitRot) {
+        double v = (double)Jt[tid];
+        for (int k = 0; k < NBETA; ++k) v += (double)Js[tid * NBETA + k] * (double)betas[k];
+        s.rest[tid] = v;
+    }
+}
+
+// prologue, lane 0, behind fit_load_body's barrier: the ancestor masks and the smoothing set-up.  Smoothing: the mean of prev over
+// the neighbours of frame f that exist and are finite; the body pose and the translation (weight w_smooth_t), never
+// the root.  wdiag is what the prior and the smoothing add to H's diagonal.
+template <class S>
+__device__ __forceinline__ void fit_lane0_setup(S& s, const double* __restrict__ prev, size_t f, int N, double w_smooth, double w_smooth_t) {
+    s.anc[0] = 0u;
+    for (int j = 1; j < NJ; ++j) s.anc[j] = s.anc[s.parents[j]] | (1u << s.parents[j]);
+    int cnt = 0;
+    bool use[2] = {false, false};
+    if (prev) {
+        for (int q = 0; q < 2; ++q) {
+            const long long g = (long long)f + (q == 0 ? -1 : 1);
+            if (g < 0 || g >= N) continue;
+            bool fin = true;
+            for (int i = 0; i < kFitX; ++i) fin = fin && isfinite(prev[(size_t)g * kFitX + i]);
+            use[q] = fin;
+            cnt += fin ? 1 : 0;
+        }
+    }
+    for (int i = 0; i < kFitX; ++i) {
+        const bool on = i >= 3 && cnt > 0;
+        double m = 0.0;
+        if (on) {
+            if (use[0]) m += prev[(f - 1) * kFitX + i];
+            if (use[1]) m += prev[(f + 1) * kFitX + i];
+            m /= (double)cnt;
+        }
+        s.mean[i] = m;
+        s.wsm[i] = on ? (i < kFitRot ? w_smooth : w_smooth_t) : 0.0;
+        s.wdiag[i] = (i < kFitRot ? s.wp[i / 3] : 0.0) + s.wsm[i];
+    }
+}
+
+// R of all joints on 22 lanes; kJac also leaves J_r in M (turned into G J_r by fit_jacobian).  Ends with a barrier.
+template <bool kJac, class S>
+__device__ __forceinline__ void fit_rotations(S& s, const double* x, int tid) {
+    if (tid < NJ) {
+        rodrigues64(x + tid * 3, s.R + tid * 9);
+        if (kJac) right_jacobian64(x + tid * 3, s.M + tid * 9);
+    }
+    __syncthreads();
+}
+
+// lane 0: the data term's energy e plus the prior and the smoothing at x
+template <class S>
+__device__ __forceinline__ double fit_prior_energy(const S& s, const double* x, double e) {
+    for (int k = 0; k < NJ; ++k) {
+        double q = 0.0, m = 0.0;
+        for (int c = 0; c < 3; ++c) {
+            const double th = x[k * 3 + c], d = th - s.mean[k * 3 + c];
+            q += th * th;
+            m += s.wsm[k * 3 + c] * (d * d);
+        }
+        e += s.wp[k] * q + m;
+    }
+    double m = 0.0;
+    for (int c = 0; c < 3; ++c) {
+        const double d = x[kFitRot + c] - s.mean[kFitRot + c];
+        m += s.wsm[kFitRot + c] * (d * d);
+    }
+    return e + m;
+}
+
+// entry i of g at s.x: the data term's v plus the prior and the smoothing
+template <class S>
+__device__ __forceinline__ double fit_prior_gradient(const S& s, int i, double v) {
+    if (i < kFitRot) return v + s.wp[i / 3] * s.x[i] + s.wsm[i] * (s.x[i] - s.mean[i]);
+    return v + s.wsm[i] * (s.x[i] - s.mean[i]);
+}
+
 // The Jacobian of the 66 joint coordinates against the 66 rotation unknowns into s.W [66 rows][66 columns], from G, P and the J_r that
 // an evaluation left in M (turned into G J_r here).  Ends with a barrier.
 template <class S>
@@ -164,6 +269,92 @@ __device__ __forceinline__ bool fit_solve(S& s, double lambda, int tid) {
         __syncthreads();
     }
     return true;
+}
+
+// H (packed) and g at s.x from the state p.evaluate<true> left: p.hessian(i, j) is the data term's share of H_ij (i >= j),
+// p.gradient(i) its share of g_i.  Ends with a barrier.
+template <class S, class Problem>
+__device__ __forceinline__ void fit_normal(S& s, const Problem& p, int tid) {
+    fit_jacobian(s, tid);
+    int i = 0, base = 0;                             // this thread's first packed index is tid: walk (i, j) along with it
+    for (int e = tid; e < kFitTri; e += kFitThreads) {
+        while (base + i + 1 <= e) { base += i + 1; ++i; }
+        const int j = e - base;
+        double v = p.hessian(i, j);
+        if (i == j) v += s.wdiag[i];
+        s.H[e] = v;
+    }
+    if (tid < kFitX) s.g[tid] = fit_prior_gradient(s, tid, p.gradient(tid));
+    __syncthreads();
+}
+
+// H and g as the rows of normal[69][70]
+template <class S>
+__device__ __forceinline__ void fit_dump_normal(const S& s, double* __restrict__ normal, int tid) {
+    for (int e = tid; e < kFitX * (kFitX + 1); e += kFitThreads) {
+        const int i = e / (kFitX + 1), j = e % (kFitX + 1);
+        normal[e] = j == kFitX ? s.g[i] : s.H[i >= j ? tri(i, j) : tri(j, i)];
+    }
+}
+
+// A frame that is not fitted: zeros, the status and NaN in the six report columns both kernels have.  The caller adds its own
+// columns and returns: the whole block leaves.
+__device__ __forceinline__ void fit_unfitted(int status, double* __restrict__ params, double* __restrict__ report, double* __restrict__ normal,
+                                             int tid) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    for (int i = tid; i < kFitX; i += kFitThreads) params[i] = 0.0;
+    if (normal)
+        for (int i = tid; i < kFitX * (kFitX + 1); i += kFitThreads) normal[i] = 0.0;
+    if (tid == 0) {
+        report[0] = (double)status; report[1] = nan; report[2] = nan; report[3] = 0.0; report[4] = nan; report[5] = nan;
+    }
+}
+
+struct FitLm { double E0, E, lambda; int accepted; };     // the energy at the start and at the answer, the last damping, the accepted tries
+
+// Levenberg-Marquardt from s.x, where E = p.evaluate<true>(s.x) has just been taken: up to `iters` iterations of up to eight tries,
+// lambda / 10 (not below 1e-9) after an accepted try and * 10 (not above 1e8) after a rejected one.  `normal`, if asked for, is H and g
+// at the start.  The answer is in s.x; the state of the last evaluation is that of the last try, not of s.x.
+template <class S, class Problem>
+__device__ __forceinline__ FitLm fit_lm(S& s, const Problem& p, double E, int iters, double* __restrict__ normal, int tid) {
+    const double E0 = E;
+    double lambda = kFitLambda0;
+    int accepted = 0;
+    bool fresh = false;                              // H and g belong to the current x
+    if (normal || iters > 0) {
+        fit_normal(s, p, tid);
+        fresh = true;
+    }
+    if (normal) fit_dump_normal(s, normal, tid);
+    for (int it = 0; it < iters; ++it) {
+        if (!fresh) {
+            E = p.template evaluate<true>(s.x);
+            fit_normal(s, p, tid);
+            fresh = true;
+        }
+        for (int tr = 0; tr < kFitTries; ++tr) {
+            bool ok = fit_solve(s, lambda, tid);
+            if (ok) {
+                if (tid < kFitX) s.xt[tid] = s.x[tid] + s.rhs[tid];
+                __syncthreads();
+                const double Et = p.template evaluate<false>(s.xt);
+                ok = Et < E;                         // an infinite (or NaN) energy is a rejected try
+                if (ok) {
+                    if (tid < kFitX) s.x[tid] = s.xt[tid];
+                    E = Et;
+                    __syncthreads();
+                }
+            }
+            if (ok) {
+                lambda = fmax(lambda / 10.0, kFitLambdaMin);
+                ++accepted;
+                fresh = false;
+                break;
+            }
+            lambda = fmin(lambda * 10.0, kFitLambdaMax);
+        }
+    }
+    return {E0, E, lambda, accepted};
 }
 
 }  // namespace rohm

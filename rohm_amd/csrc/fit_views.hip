@@ -5,24 +5,23 @@
 // This is rohm_fit_pose (fit.hip) with a symmetric 3 x 3 weight per joint where that kernel has a scalar: the data term's normal
 // equations are H = sum_j Jp_j^T W_j Jp_j, g = sum_j Jp_j^T b_j, with W_j = sum_v w_vj A_vj^T A_vj and b_j = sum_v w_vj A_vj^T r_vj
 // taken over the views in ascending order by the joint's own lane.  The quadratic forms are formed on the fly from the 66 x 66
-// joint Jacobian, so there is no second 66 x 66 array.  The float64 helpers, the Jacobian and the Cholesky solve are fit_math.h's,
-// shared with fit.hip.  All arithmetic is float64 on the float32 inputs.  No atomics, every sum is taken by one thread in a fixed
-// order: the same input gives the same bits.
+// joint Jacobian, so there is no second 66 x 66 array.  Only that data term (FitViewsProblem), the start translation and the report
+// are here: the solver (its LDS, the prologue pieces, the prior and smoothing, the walk over H, the Cholesky solve, the
+// iteration, the unfitted exit) is fit_math.h's; the camera row (observed, undistortion, projection with
+// residual and Jacobian rows, the 3 x 3 solve) is camera_math.h's, shared with multiview.hip.  All arithmetic is float64 on the
+// float32 inputs.  No atomics, every sum is taken by one thread in a fixed order: the same input gives the same bits.
 //
 // One workgroup of 256 threads per frame.  LDS, as float64: fit.hip's 64.9 KiB (H packed, the Jacobian / Cholesky factor, the
 // per-joint state) plus the undistorted observations (a, b, c) of every (view, joint), 8.3 KiB at the limit of 16 views, 14 values
 // per camera row (1.8 KiB) and the per-joint W_j, b_j and partial sums (2.3 KiB): 76.0 KiB whatever V is, so two workgroups share a
 // CU's 160 KiB as in fit.hip.  The undistortion runs once, in the prologue, (view, joint) entries across the threads.
+#include "camera_math.h"
 #include "fit_math.h"
 #include "../../include/rohm_fit_views.h"
 
-#include <math.h>
-
 namespace rohm {
 
-constexpr int kFvMaxViews = 16;
-constexpr int kFvCamIn = 24;                         // a row of `cams`: R (9), t (3), fx, fy, cx, cy, k1, k2, p1, p2, k3, three zeros
-constexpr int kFvCam = 14;                           // what the iteration needs of it: R, t, fx, fy
+constexpr int kFvMaxViews = 16;                      // (of a camera row's 24 values the iteration keeps kCamPinhole = 14: R, t, fx, fy)
 constexpr int kFvReport = 8;
 constexpr double kFvSingular = 1e-12;                // the start translation's system is singular when det <= this * trace^3
 
@@ -44,166 +43,113 @@ struct FitViewsArgs {
     double* normal;               // [N,69,70] or null
 };
 
-struct FitViewsShared {
-    double H[kFitTri];            // packed lower triangle
-    double W[kFitRot * kFitRot];  // the Jacobian [66 rows][66 columns]; then the packed Cholesky factor
-    double g[kFitX], dg[kFitX], rhs[kFitX], sol[kFitX];
-    double x[kFitX], xt[kFitX];
-    double R[NJ * 9], G[NJ * 9], M[NJ * 9];          // local and world rotations; M = G J_r
-    double P[NJ * 3], rest[NJ * 3];
-    double mean[kFitX], wdiag[kFitX], wsm[kFitX], wp[NJ];    // (the translation's three entries carry the smoothing only)
+struct FitViewsShared : FitCore {
     double Wj[NJ * 6], bj[NJ * 3];                   // per joint: W_j as (00, 01, 02, 11, 12, 22) and b_j
     double ej[NJ], ce2[NJ], sc[NJ], zmin[NJ];        // per joint: sum_v c rho(e2) (infinite behind a camera), sum_v c e2, sum_v c, min z_c
     double obs[kFvMaxViews * NJ * 3];                // (a, b, c) per (view, joint); c = 0 where unobserved
-    double cam[kFvMaxViews * kFvCam];
-    double E;
-    int parents[NJ];
-    unsigned anc[NJ];             // bit k: joint k is a strict ancestor
-    int status, n_obs, solve_t;
+    double cam[kFvMaxViews * kCamPinhole];
+    int n_obs, solve_t;
 #ifdef ROHM_FIT_VIEWS_ONE_WORKGROUP                  // the A/B build of scripts/bench_fit_views.py: past 80 KiB a workgroup has its CU to itself
     double one_workgroup_pad[1024];
 #endif
 };
-
-// rule 1 of rohm_multiview.h (mv_undistort of multiview.hip): five fixed-point iterations, no mirroring
-__device__ __forceinline__ void fv_undistort(const double* cam, double px, double py, double& a, double& b) {
-    const double k1 = cam[16], k2 = cam[17], p1 = cam[18], p2 = cam[19], k3 = cam[20];
-    const double x0 = (px - cam[14]) / cam[12], y0 = (py - cam[15]) / cam[13];
-    double x = x0, y = y0;
-#pragma unroll 1
-    for (int it = 0; it < 5; ++it) {
-        const double r2 = x * x + y * y;
-        const double icd = 1.0 / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2);
-        const double dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x);
-        const double dy = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y;
-        x = (x0 - dx) * icd;
-        y = (y0 - dy) * icd;
-    }
-    a = x;
-    b = y;
-}
-
-// R, J_r on 22 lanes, the chain on lane 0.  Ends with a barrier.
-template <bool kJac>
-__device__ __forceinline__ void fv_kinematics(FitViewsShared& s, const double* x, int tid) {
-    if (tid < NJ) {
-        rodrigues64(x + tid * 3, s.R + tid * 9);
-        if (kJac) right_jacobian64(x + tid * 3, s.M + tid * 9);
-    }
-    __syncthreads();
-    if (tid == 0) chain64(s.R, s.rest, s.parents, s.G, s.P);
-    __syncthreads();
-}
-
-// Joint j against its observations at X = P_j + t, the views in ascending order: e_j, sum c e2, sum c, min z_c and, with kJac, W_j and
-// b_j.  `resid` (this frame's [V][.][22] rows, stride `vstride` between views) receives sqrt(e2), NaN where unobserved.
-template <bool kJac>
-__device__ __forceinline__ void fv_joint(FitViewsShared& s, const double* x, int j, int V, double sigma2, double* resid, size_t vstride) {
-    const double X[3] = {s.P[j * 3] + x[kFitRot], s.P[j * 3 + 1] + x[kFitRot + 1], s.P[j * 3 + 2] + x[kFitRot + 2]};
-    double e = 0.0, ce2 = 0.0, sc = 0.0, zmin = (double)INFINITY;
-    double Wq[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, bq[3] = {0.0, 0.0, 0.0};
-    bool behind = false;
-    for (int v = 0; v < V; ++v) {
-        const double* o = s.obs + (v * NJ + j) * 3;
-        const double c = o[2];
-        double out = __longlong_as_double(0x7ff8000000000000ll);
-        if (c > 0.0) {
-            const double* cam = s.cam + v * kFvCam;
-            const double xc = cam[0] * X[0] + cam[1] * X[1] + cam[2] * X[2] + cam[9];
-            const double yc = cam[3] * X[0] + cam[4] * X[1] + cam[5] * X[2] + cam[10];
-            const double zc = cam[6] * X[0] + cam[7] * X[1] + cam[8] * X[2] + cam[11];
-            zmin = fmin(zmin, zc);
-            if (zc > 0.0) {
-                const double u = xc / zc, w = yc / zc;
-                const double r0 = cam[12] * (u - o[0]), r1 = cam[13] * (w - o[1]);
-                const double e2 = r0 * r0 + r1 * r1;
-                double rho = e2, drho = 1.0;
-                if (sigma2 > 0.0) {
-                    const double q = sigma2 / (sigma2 + e2);
-                    rho = q * e2;
-                    drho = q * q;
-                }
-                e += c * rho;
-                ce2 += c * e2;
-                sc += c;
-                out = sqrt(e2);
-                if (kJac) {
-                    const double wv = c * drho;
-                    double j0[3], j1[3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        j0[k] = cam[12] * (cam[k] - u * cam[6 + k]) / zc;
-                        j1[k] = cam[13] * (cam[3 + k] - w * cam[6 + k]) / zc;
-                    }
-                    Wq[0] += wv * (j0[0] * j0[0] + j1[0] * j1[0]);
-                    Wq[1] += wv * (j0[0] * j0[1] + j1[0] * j1[1]);
-                    Wq[2] += wv * (j0[0] * j0[2] + j1[0] * j1[2]);
-                    Wq[3] += wv * (j0[1] * j0[1] + j1[1] * j1[1]);
-                    Wq[4] += wv * (j0[1] * j0[2] + j1[1] * j1[2]);
-                    Wq[5] += wv * (j0[2] * j0[2] + j1[2] * j1[2]);
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) bq[k] += wv * (j0[k] * r0 + j1[k] * r1);
-                }
-            } else {
-                behind = true;
-            }
-        }
-        if (resid) resid[(size_t)v * vstride + j] = out;
-    }
-    s.ej[j] = behind ? (double)INFINITY : e;
-    s.ce2[j] = ce2;
-    s.sc[j] = sc;
-    s.zmin[j] = zmin;
-    if (kJac) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) s.Wj[j * 6 + k] = Wq[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) s.bj[j * 3 + k] = bq[k];
-    }
-}
-
-// E at x; every thread returns it.  kJac also leaves J_r in M, W_j and b_j for fv_normal.
-template <bool kJac>
-__device__ __forceinline__ double fv_evaluate(FitViewsShared& s, const double* x, int tid, int V, double sigma2, double* resid = nullptr,
-                                              size_t vstride = 0) {
-    fv_kinematics<kJac>(s, x, tid);
-    if (tid < NJ) fv_joint<kJac>(s, x, tid, V, sigma2, resid, vstride);
-    __syncthreads();
-    if (tid == 0) {
-        double e = 0.0;
-        for (int j = 0; j < NJ; ++j) e += s.ej[j];
-        for (int k = 0; k < NJ; ++k) {
-            double q = 0.0, m = 0.0;
-            for (int c = 0; c < 3; ++c) {
-                const double th = x[k * 3 + c], d = th - s.mean[k * 3 + c];
-                q += th * th;
-                m += s.wsm[k * 3 + c] * (d * d);
-            }
-            e += s.wp[k] * q + m;
-        }
-        double m = 0.0;
-        for (int c = 0; c < 3; ++c) {
-            const double d = x[kFitRot + c] - s.mean[kFitRot + c];
-            m += s.wsm[kFitRot + c] * (d * d);
-        }
-        s.E = e + m;
-    }
-    __syncthreads();
-    return s.E;
-}
 
 __device__ __forceinline__ double fv_sym(const double* Wq, int a, int b) {        // entry (a, b) of (00, 01, 02, 11, 12, 22)
     const int lo = a < b ? a : b, hi = a < b ? b : a;
     return Wq[lo == 0 ? hi : (lo == 1 ? 2 + hi : 5)];
 }
 
-// H (packed) and g at s.x from the state fv_evaluate<true> left
-__device__ __forceinline__ void fv_normal(FitViewsShared& s, int tid) {
-    fit_jacobian(s, tid);
-    int i = 0, base = 0;                             // this thread's first packed index is tid: walk (i, j) along with it
-    for (int e = tid; e < kFitTri; e += kFitThreads) {
-        while (base + i + 1 <= e) { base += i + 1; ++i; }
-        const int j = e - base;
+// The data term sum_v sum_j c_vj rho(|r_vj|^2) for fit_lm.
+struct FitViewsProblem {
+    FitViewsShared& s;
+    int tid, V;
+    double sigma2;
+
+    // R, J_r on 22 lanes, the chain on lane 0.  Ends with a barrier.
+    template <bool kJac>
+    __device__ __forceinline__ void kinematics(const double* x) const {
+        fit_rotations<kJac>(s, x, tid);
+        if (tid == 0) chain64(s.R, s.rest, s.parents, s.G, s.P);
+        __syncthreads();
+    }
+
+    // Joint j against its observations at X = P_j + t, the views in ascending order: e_j, sum c e2, sum c, min z_c and, with kJac, W_j
+    // and b_j.  `resid` (this frame's [V][.][22] rows, stride `vstride` between views) receives sqrt(e2), NaN where unobserved.
+    template <bool kJac>
+    __device__ __forceinline__ void joint(const double* x, int j, double* resid, size_t vstride) const {
+        const double X[3] = {s.P[j * 3] + x[kFitRot], s.P[j * 3 + 1] + x[kFitRot + 1], s.P[j * 3 + 2] + x[kFitRot + 2]};
+        double e = 0.0, ce2 = 0.0, sc = 0.0, zmin = (double)INFINITY;
+        double Wq[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, bq[3] = {0.0, 0.0, 0.0};
+        bool behind = false;
+        for (int v = 0; v < V; ++v) {
+            const double* o = s.obs + (v * NJ + j) * 3;
+            const double c = o[2];
+            double out = __longlong_as_double(0x7ff8000000000000ll);
+            if (c > 0.0) {
+                const double* cam = s.cam + v * kCamPinhole;
+                double Xc[3];
+                cam_to_view(cam, X, Xc);
+                zmin = fmin(zmin, Xc[2]);
+                if (Xc[2] > 0.0) {
+                    double r[2], j0[3], j1[3];
+                    const double e2 = cam_residual<kJac>(cam, X, o[0], o[1], r, j0, j1);
+                    double rho = e2, drho = 1.0;
+                    if (sigma2 > 0.0) {
+                        const double q = sigma2 / (sigma2 + e2);
+                        rho = q * e2;
+                        drho = q * q;
+                    }
+                    e += c * rho;
+                    ce2 += c * e2;
+                    sc += c;
+                    out = sqrt(e2);
+                    if (kJac) {
+                        const double wv = c * drho;
+                        Wq[0] += wv * (j0[0] * j0[0] + j1[0] * j1[0]);
+                        Wq[1] += wv * (j0[0] * j0[1] + j1[0] * j1[1]);
+                        Wq[2] += wv * (j0[0] * j0[2] + j1[0] * j1[2]);
+                        Wq[3] += wv * (j0[1] * j0[1] + j1[1] * j1[1]);
+                        Wq[4] += wv * (j0[1] * j0[2] + j1[1] * j1[2]);
+                        Wq[5] += wv * (j0[2] * j0[2] + j1[2] * j1[2]);
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) bq[k] += wv * (j0[k] * r[0] + j1[k] * r[1]);
+                    }
+                } else {
+                    behind = true;
+                }
+            }
+            if (resid) resid[(size_t)v * vstride + j] = out;
+        }
+        s.ej[j] = behind ? (double)INFINITY : e;
+        s.ce2[j] = ce2;
+        s.sc[j] = sc;
+        s.zmin[j] = zmin;
+        if (kJac) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) s.Wj[j * 6 + k] = Wq[k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s.bj[j * 3 + k] = bq[k];
+        }
+    }
+
+    // E at x; every thread returns it.  kJac also leaves J_r in M, W_j and b_j for hessian() and gradient().
+    template <bool kJac>
+    __device__ __forceinline__ double evaluate(const double* x, double* resid = nullptr, size_t vstride = 0) const {
+        kinematics<kJac>(x);
+        if (tid < NJ) joint<kJac>(x, tid, resid, vstride);
+        __syncthreads();
+        if (tid == 0) {
+            double e = 0.0;
+            for (int j = 0; j < NJ; ++j) e += s.ej[j];
+            s.E = fit_prior_energy(s, x, e);
+        }
+        __syncthreads();
+        return s.E;
+    }
+
+    // the data term's share of H_ij (i >= j) and of g_i: sum_q Jp_q^T W_q Jp_q and sum_q Jp_q^T b_q, the translation's columns of Jp
+    // being the identity
+    __device__ __forceinline__ double hessian(int i, int j) const {
         double v = 0.0;
         if (i < kFitRot) {
             for (int q = 0; q < NJ; ++q) {
@@ -224,66 +170,54 @@ __device__ __forceinline__ void fv_normal(FitViewsShared& s, int tid) {
         } else {
             for (int q = 0; q < NJ; ++q) v += fv_sym(s.Wj + q * 6, i - kFitRot, j - kFitRot);
         }
-        if (i == j) v += s.wdiag[i];
-        s.H[e] = v;
+        return v;
     }
-    if (tid < kFitRot) {
+    __device__ __forceinline__ double gradient(int i) const {
         double v = 0.0;
-        for (int q = 0; q < NJ; ++q) {
-            const double* row = s.W + (q * 3) * kFitRot;
-            v += row[tid] * s.bj[q * 3] + row[kFitRot + tid] * s.bj[q * 3 + 1] + row[2 * kFitRot + tid] * s.bj[q * 3 + 2];
+        if (i < kFitRot) {
+            for (int q = 0; q < NJ; ++q) {
+                const double* row = s.W + (q * 3) * kFitRot;
+                v += row[i] * s.bj[q * 3] + row[kFitRot + i] * s.bj[q * 3 + 1] + row[2 * kFitRot + i] * s.bj[q * 3 + 2];
+            }
+        } else {
+            for (int q = 0; q < NJ; ++q) v += s.bj[q * 3 + i - kFitRot];
         }
-        s.g[tid] = v + s.wp[tid / 3] * s.x[tid] + s.wsm[tid] * (s.x[tid] - s.mean[tid]);
-    } else if (tid < kFitX) {
-        double v = 0.0;
-        for (int q = 0; q < NJ; ++q) v += s.bj[q * 3 + tid - kFitRot];
-        s.g[tid] = v + s.wsm[tid] * (s.x[tid] - s.mean[tid]);
+        return v;
     }
-    __syncthreads();
-}
+};
 
-// Two waves per SIMD, as fit_pose_kernel: 76 KiB of LDS lets two workgroups share a CU only if the kernel stays within 256 registers
-// (it takes 255, no spills).  Measured for 3 000 frames of 20 iterations at V = 1 / 4 / 16: 41 / 58 / 60 ms, against 71 / 104 / 107 ms with
+// Two waves per SIMD, as fit_pose_kernel: 76 KiB of LDS lets two workgroups share a CU only if the kernel stays within 256 registers.
+// Measured for 3 000 frames of 20 iterations at V = 1 / 4 / 16: 41 / 58 / 60 ms, against 71 / 104 / 107 ms with
 // one workgroup per CU (profiles/fit_views_bench.json, profiles/fit_views_bench_one_workgroup_per_cu.json).
 __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(2))) void fit_views_pose_kernel(const FitViewsArgs a) {
     __shared__ FitViewsShared s;
     const int tid = threadIdx.x;
     const size_t f = blockIdx.x;
     const int V = a.V;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
     double* params = a.params + f * kFitX;
     double* report = a.report + f * kFvReport;
     double* normal = a.normal ? a.normal + f * kFitX * (kFitX + 1) : nullptr;
     double* resid = a.resid ? a.resid + f * NJ : nullptr;            // view v's row of this frame is at resid + v * N * 22
     const size_t vstride = (size_t)a.N * NJ;
     const double* init = a.init + f * kFitX;
+    const FitViewsProblem prob = {s, tid, V, a.sigma2};
 
-    // ---- prologue: observations (undistorted once), camera rows, the rest joints
+    // ---- prologue: observations (undistorted once), camera rows, the body
     for (int e = tid; e < V * NJ; e += kFitThreads) {
         const int v = e / NJ, j = e % NJ;
         const float* k = a.kp + (((size_t)v * a.N + f) * NJ + j) * 3;
         const double px = (double)k[0], py = (double)k[1], c = (double)k[2];
-        const bool ok = isfinite(px) && isfinite(py) && isfinite(c) && c > a.conf_min;
+        const bool ok = cam_observed(px, py, c, a.conf_min);
         double ua = 0.0, ub = 0.0;
-        if (ok) fv_undistort(a.cams + (size_t)v * kFvCamIn, px, py, ua, ub);
+        if (ok) cam_undistort(a.cams + (size_t)v * kCamRow, px, py, ua, ub);
         s.obs[e * 3] = ua;
         s.obs[e * 3 + 1] = ub;
         s.obs[e * 3 + 2] = ok ? c : 0.0;
     }
-    for (int e = tid; e < V * kFvCam; e += kFitThreads) s.cam[e] = a.cams[(size_t)(e / kFvCam) * kFvCamIn + e % kFvCam];
-    if (tid < NJ) {
-        s.parents[tid] = a.parents[tid];
-        s.wp[tid] = a.w_prior[tid];
-    }
-    if (tid < kFitRot) {
-        double v = (double)a.Jt[tid];
-        for (int k = 0; k < NBETA; ++k) v += (double)a.Js[tid * NBETA + k] * (double)a.betas[f * NBETA + k];
-        s.rest[tid] = v;
-    }
+    for (int e = tid; e < V * kCamPinhole; e += kFitThreads) s.cam[e] = a.cams[(size_t)(e / kCamPinhole) * kCamRow + e % kCamPinhole];
+    fit_load_body(s, a.Jt, a.Js, a.parents, a.betas + f * NBETA, a.w_prior, tid);
     __syncthreads();
     if (tid == 0) {
-        s.anc[0] = 0u;
-        for (int j = 1; j < NJ; ++j) s.anc[j] = s.anc[s.parents[j]] | (1u << s.parents[j]);
         int seen = 0;
         for (int e = 0; e < V * NJ; ++e) seen += s.obs[e * 3 + 2] > 0.0 ? 1 : 0;
         s.n_obs = seen;
@@ -298,31 +232,7 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(2))
         s.status = status;
         s.solve_t = t_nan ? 1 : 0;
         for (int i = 0; i < kFitX; ++i) s.x[i] = (status == 1 && !(t_nan && i >= kFitRot)) ? init[i] : 0.0;
-        // smoothing: the mean of prev over the neighbours that exist and are finite; body pose and translation, not the root
-        int cnt = 0;
-        bool use[2] = {false, false};
-        if (a.prev) {
-            for (int q = 0; q < 2; ++q) {
-                const long long g = (long long)f + (q == 0 ? -1 : 1);
-                if (g < 0 || g >= a.N) continue;
-                bool fin = true;
-                for (int i = 0; i < kFitX; ++i) fin = fin && isfinite(a.prev[(size_t)g * kFitX + i]);
-                use[q] = fin;
-                cnt += fin ? 1 : 0;
-            }
-        }
-        for (int i = 0; i < kFitX; ++i) {
-            const bool on = i >= 3 && cnt > 0;
-            double m = 0.0;
-            if (on) {
-                if (use[0]) m += a.prev[(f - 1) * kFitX + i];
-                if (use[1]) m += a.prev[(f + 1) * kFitX + i];
-                m /= (double)cnt;
-            }
-            s.mean[i] = m;
-            s.wsm[i] = on ? (i < kFitRot ? a.w_smooth : a.w_smooth_t) : 0.0;
-            s.wdiag[i] = (i < kFitRot ? s.wp[i / 3] : 0.0) + s.wsm[i];
-        }
+        fit_lane0_setup(s, a.prev, f, a.N, a.w_smooth, a.w_smooth_t);        // smoothing: body pose and translation, not the root
     }
     __syncthreads();
 
@@ -330,7 +240,7 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(2))
     double E = 0.0;
     if (s.status == 1) {                             // (uniform: read after the barrier, written again only behind the next one)
         if (s.solve_t) {
-            fv_kinematics<false>(s, s.x, tid);
+            prob.kinematics<false>(s.x);
             if (tid < NJ) {                          // joint j's share of sum c (n1 n1^T + n2 n2^T) t = -sum c (n1 (n1 . p + d1) + n2 (n2 . p + d2))
                 double A[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, r[3] = {0.0, 0.0, 0.0};
                 const double* p = s.P + tid * 3;
@@ -338,7 +248,7 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(2))
                     const double* o = s.obs + (v * NJ + tid) * 3;
                     const double c = o[2];
                     if (!(c > 0.0)) continue;
-                    const double* cam = s.cam + v * kFvCam;
+                    const double* cam = s.cam + v * kCamPinhole;
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const double n0 = cam[h * 3] - o[h] * cam[6], n1 = cam[h * 3 + 1] - o[h] * cam[7], n2 = cam[h * 3 + 2] - o[h] * cam[8];
@@ -353,18 +263,14 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(2))
             }
             __syncthreads();
             if (tid == 0) {
-                double A[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};
+                double A[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0}, t[3];
                 for (int j = 0; j < NJ; ++j) {
                     for (int k = 0; k < 6; ++k) A[k] += s.Wj[j * 6 + k];
                     for (int k = 0; k < 3; ++k) b[k] += s.bj[j * 3 + k];
                 }
-                const double c00 = A[3] * A[5] - A[4] * A[4], c01 = A[2] * A[4] - A[1] * A[5], c02 = A[1] * A[4] - A[2] * A[3];
-                const double c11 = A[0] * A[5] - A[2] * A[2], c12 = A[1] * A[2] - A[0] * A[4], c22 = A[0] * A[3] - A[1] * A[1];
-                const double det = A[0] * c00 + A[1] * c01 + A[2] * c02, tr = A[0] + A[3] + A[5];
+                const double det = cam_solve3(A, b, t).det, tr = A[0] + A[3] + A[5];
                 if (det > kFvSingular * (tr * tr * tr)) {
-                    s.x[kFitRot] = (c00 * b[0] + c01 * b[1] + c02 * b[2]) / det;
-                    s.x[kFitRot + 1] = (c01 * b[0] + c11 * b[1] + c12 * b[2]) / det;
-                    s.x[kFitRot + 2] = (c02 * b[0] + c12 * b[1] + c22 * b[2]) / det;
+                    for (int k = 0; k < 3; ++k) s.x[kFitRot + k] = t[k];
                 } else {
                     s.status = 3;
                 }
@@ -372,7 +278,7 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(2))
             __syncthreads();
         }
         if (s.status == 1) {
-            E = fv_evaluate<true>(s, s.x, tid, V, a.sigma2);
+            E = prob.evaluate<true>(s.x);
             if (!(E < (double)INFINITY)) {           // an observed joint at z_c <= 0 (or a start that is not a number)
                 if (tid == 0) s.status = 3;
             }
@@ -380,62 +286,19 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(2))
         }
     }
     const int status = s.status;
-    if (status != 1) {                               // zeros and NaN; the whole block leaves
-        for (int i = tid; i < kFitX; i += kFitThreads) params[i] = 0.0;
-        if (normal)
-            for (int i = tid; i < kFitX * (kFitX + 1); i += kFitThreads) normal[i] = 0.0;
+    if (status != 1) {
+        fit_unfitted(status, params, report, normal, tid);
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
         if (resid)
             for (int e = tid; e < V * NJ; e += kFitThreads) resid[(size_t)(e / NJ) * vstride + e % NJ] = nan;
         if (tid == 0) {
-            report[0] = (double)status; report[1] = nan; report[2] = nan; report[3] = 0.0; report[4] = nan; report[5] = nan;
             report[6] = (double)s.n_obs; report[7] = nan;
         }
         return;
     }
 
-    const double E0 = E;
-    double lambda = kFitLambda0;
-    int accepted = 0;
-    bool fresh = false;                              // H and g belong to the current x
-    if (normal || a.iters > 0) {
-        fv_normal(s, tid);
-        fresh = true;
-    }
-    if (normal) {
-        for (int e = tid; e < kFitX * (kFitX + 1); e += kFitThreads) {
-            const int i = e / (kFitX + 1), j = e % (kFitX + 1);
-            normal[e] = j == kFitX ? s.g[i] : s.H[i >= j ? tri(i, j) : tri(j, i)];
-        }
-    }
-    for (int it = 0; it < a.iters; ++it) {
-        if (!fresh) {
-            E = fv_evaluate<true>(s, s.x, tid, V, a.sigma2);
-            fv_normal(s, tid);
-            fresh = true;
-        }
-        for (int tr = 0; tr < kFitTries; ++tr) {
-            bool ok = fit_solve(s, lambda, tid);
-            if (ok) {
-                if (tid < kFitX) s.xt[tid] = s.x[tid] + s.rhs[tid];
-                __syncthreads();
-                const double Et = fv_evaluate<false>(s, s.xt, tid, V, a.sigma2);
-                ok = Et < E;                         // an infinite (or NaN) energy is a rejected try
-                if (ok) {
-                    if (tid < kFitX) s.x[tid] = s.xt[tid];
-                    E = Et;
-                    __syncthreads();
-                }
-            }
-            if (ok) {
-                lambda = fmax(lambda / 10.0, kFitLambdaMin);
-                ++accepted;
-                fresh = false;
-                break;
-            }
-            lambda = fmin(lambda * 10.0, kFitLambdaMax);
-        }
-    }
-    fv_evaluate<false>(s, s.x, tid, V, a.sigma2, resid, vstride);    // the residuals at the answer
+    const FitLm lm = fit_lm(s, prob, E, a.iters, normal, tid);
+    prob.evaluate<false>(s.x, resid, vstride);       // the residuals at the answer
     if (tid < kFitX) params[tid] = s.x[tid];
     if (tid == 0) {
         double sc = 0.0, sr = 0.0, zmin = (double)INFINITY;
@@ -444,7 +307,7 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(2))
             sr += s.ce2[j];
             zmin = fmin(zmin, s.zmin[j]);
         }
-        report[0] = 1.0; report[1] = E0; report[2] = E; report[3] = (double)accepted; report[4] = lambda; report[5] = sqrt(sr / sc);
+        report[0] = 1.0; report[1] = lm.E0; report[2] = lm.E; report[3] = (double)lm.accepted; report[4] = lm.lambda; report[5] = sqrt(sr / sc);
         report[6] = (double)s.n_obs; report[7] = zmin;
     }
 }

@@ -3,7 +3,8 @@
 // restates both in numpy; include/rohm_multiview.h states the rule in full.  There is no counterpart in the reference: its
 // EgoBody loader reads the calibration of five Kinects and uses one view.
 //
-// All arithmetic is float64 on the float32 keypoints, as in fit.hip and floor.hip.  No atomics, every sum is taken in a fixed
+// The camera row (observed, undistortion, projection with residual and Jacobian rows, the 3 x 3 cofactor solve) is camera_math.h's,
+// shared with fit_views.hip.  All arithmetic is float64 on the float32 keypoints, as in fit.hip and floor.hip.  No atomics, every sum is taken in a fixed
 // order or by a fixed butterfly: the same input gives the same bits.
 //
 // rohm_mv_triangulate: a group of W lanes per (frame, joint) in workgroups of 256 threads.  W = 64, a wave, serves any V; up to
@@ -16,10 +17,10 @@
 // holds view v's camera and detection in registers, the 3 x 3 normal equations are 16-lane xor-butterflies, the same at either
 // W, so both widths give the same bits.  One thread per point with 16 rays in registers spills; a group per point does not.
 #include "common.h"
+#include "camera_math.h"
 #include "../../include/rohm_multiview.h"
 
 #include <limits.h>
-#include <math.h>
 
 namespace rohm {
 
@@ -27,7 +28,6 @@ constexpr int kMvMaxViews = 16;
 constexpr int kMvMaxPairs = kMvMaxViews * (kMvMaxViews - 1) / 2;
 constexpr int kMvThreads = 256;
 constexpr int kMvSmallViews = 6;                     // up to this many views the pairs (15) fit a group of 16 lanes
-constexpr int kMvCam = 24;                           // R (9), t (3), fx, fy, cx, cy, k1, k2, p1, p2, k3, three zeros
 constexpr int kMvRay = 9;                            // o (3), d (3), a, b, c
 constexpr int kMvMaxRefine = 64;
 constexpr long long kMvMaxPoints = 1ll << 29;
@@ -46,43 +46,6 @@ struct MvArgs {
     float* kp_und;
 };
 
-// rule 1: observed, and the five fixed-point iterations of cv2.undistortPoints (keypoints_undistort_kernel without the mirroring)
-__device__ __forceinline__ bool mv_observed(double x, double y, double c, double conf_min) {
-    return isfinite(x) && isfinite(y) && isfinite(c) && c > conf_min;
-}
-
-__device__ __forceinline__ void mv_undistort(const double* cam, double px, double py, double& a, double& b) {
-    const double k1 = cam[16], k2 = cam[17], p1 = cam[18], p2 = cam[19], k3 = cam[20];
-    const double x0 = (px - cam[14]) / cam[12], y0 = (py - cam[15]) / cam[13];
-    double x = x0, y = y0;
-#pragma unroll 1
-    for (int it = 0; it < 5; ++it) {
-        const double r2 = x * x + y * y;
-        const double icd = 1.0 / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2);
-        const double dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x);
-        const double dy = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y;
-        x = (x0 - dx) * icd;
-        y = (y0 - dy) * icd;
-    }
-    a = x;
-    b = y;
-}
-
-// x = A^-1 b through the cofactors of the symmetric A = (a00, a01, a02, a11, a12, a22); returns trace(A^-1)
-__device__ __forceinline__ double mv_solve3(const double* A, const double* b, double* x) {
-    const double c00 = A[3] * A[5] - A[4] * A[4];
-    const double c01 = A[2] * A[4] - A[1] * A[5];
-    const double c02 = A[1] * A[4] - A[2] * A[3];
-    const double c11 = A[0] * A[5] - A[2] * A[2];
-    const double c12 = A[1] * A[2] - A[0] * A[4];
-    const double c22 = A[0] * A[3] - A[1] * A[1];
-    const double det = A[0] * c00 + A[1] * c01 + A[2] * c02;
-    x[0] = (c00 * b[0] + c01 * b[1] + c02 * b[2]) / det;
-    x[1] = (c01 * b[0] + c11 * b[1] + c12 * b[2]) / det;
-    x[2] = (c02 * b[0] + c12 * b[1] + c22 * b[2]) / det;
-    return (c00 + c11 + c22) / det;
-}
-
 // w (I - d d^T) and w (I - d d^T) o of one ray, the terms of the midpoint system
 __device__ __forceinline__ void mv_ray_terms(double w, const double* o, const double* d, double* A, double* b) {
     const double od = d[0] * o[0] + d[1] * o[1] + d[2] * o[2];
@@ -95,25 +58,6 @@ __device__ __forceinline__ void mv_ray_terms(double w, const double* o, const do
     b[0] = w * (o[0] - d[0] * od);
     b[1] = w * (o[1] - d[1] * od);
     b[2] = w * (o[2] - d[2] * od);
-}
-
-// the residual r of a view at X and, on request, the rows of its 2 x 3 Jacobian; returns |r|^2, infinite when z_c <= 0
-template <bool WITH_J>
-__device__ __forceinline__ double mv_residual(const double* cam, const double* X, double a, double b, double* r, double* j0, double* j1) {
-    const double xc = cam[0] * X[0] + cam[1] * X[1] + cam[2] * X[2] + cam[9];
-    const double yc = cam[3] * X[0] + cam[4] * X[1] + cam[5] * X[2] + cam[10];
-    const double zc = cam[6] * X[0] + cam[7] * X[1] + cam[8] * X[2] + cam[11];
-    const double u = xc / zc, v = yc / zc;
-    r[0] = cam[12] * (u - a);
-    r[1] = cam[13] * (v - b);
-    if (WITH_J) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            j0[k] = cam[12] * (cam[k] - u * cam[6 + k]) / zc;
-            j1[k] = cam[13] * (cam[3 + k] - v * cam[6 + k]) / zc;
-        }
-    }
-    return zc > 0.0 ? r[0] * r[0] + r[1] * r[1] : (double)INFINITY;
 }
 
 // the sum over lanes 0..15 (a fixed xor-butterfly), in every one of them
@@ -144,14 +88,14 @@ __global__ __launch_bounds__(kMvThreads) void mv_triangulate_kernel(const MvArgs
     if (live && lane < V) {
         const size_t at = ((size_t)lane * (size_t)P + (size_t)p) * 3;
         const float xf = g.kp[at], yf = g.kp[at + 1], cf = g.kp[at + 2];
-        const double* row = g.cams + (size_t)lane * kMvCam;
+        const double* row = g.cams + (size_t)lane * kCamRow;
         float ux = xf, uy = yf;
-        obs = mv_observed((double)xf, (double)yf, (double)cf, g.conf_min);
+        obs = cam_observed((double)xf, (double)yf, (double)cf, g.conf_min);
         if (obs) {
 #pragma unroll
             for (int k = 0; k < 14; ++k) cam[k] = row[k];
             c = (double)cf;
-            mv_undistort(row, (double)xf, (double)yf, a, b);
+            cam_undistort(row, (double)xf, (double)yf, a, b);
             ux = (float)(row[12] * a + row[14]);
             uy = (float)(row[13] * b + row[15]);
             double n2 = 0.0;
@@ -208,7 +152,7 @@ __global__ __launch_bounds__(kMvThreads) void mv_triangulate_kernel(const MvArgs
         for (int k = 0; k < 6; ++k) A1[k] += A2[k];
 #pragma unroll
         for (int k = 0; k < 3; ++k) b1[k] += b2[k];
-        mv_solve3(A1, b1, X);
+        cam_solve3(A1, b1, X);
         int n = 0;
         double cost = 0.0;
         unsigned mask = 0u;
@@ -216,7 +160,7 @@ __global__ __launch_bounds__(kMvThreads) void mv_triangulate_kernel(const MvArgs
             if (!((S >> v) & 1u)) continue;
             const double* ray = rays[wave][v];
             double r[2];
-            const double e2 = mv_residual<false>(g.cams + (size_t)v * kMvCam, X, ray[6], ray[7], r, nullptr, nullptr);
+            const double e2 = cam_residual<false>(g.cams + (size_t)v * kCamRow, X, ray[6], ray[7], r, nullptr, nullptr);
             if (sqrt(e2) <= g.tau) {
                 ++n;
                 cost += ray[8] * e2;
@@ -270,7 +214,7 @@ __global__ __launch_bounds__(kMvThreads) void mv_triangulate_kernel(const MvArgs
         for (int k = 0; k < 6; ++k) A[k] = mv_sum16(inl ? At[k] : 0.0);
 #pragma unroll
         for (int k = 0; k < 3; ++k) t3[k] = mv_sum16(inl ? bt[k] : 0.0);
-        mv_solve3(A, t3, X0);
+        cam_solve3(A, t3, X0);
     }
     const double sum_c = mv_sum16(w);
 #pragma unroll
@@ -278,7 +222,7 @@ __global__ __launch_bounds__(kMvThreads) void mv_triangulate_kernel(const MvArgs
     double E0 = 0.0, E = 0.0;
     for (int it = 0; it <= g.refine; ++it) {
         double r[2], j0[3], j1[3];
-        const double e2 = mv_residual<true>(cam, X, a, b, r, j0, j1);
+        const double e2 = cam_residual<true>(cam, X, a, b, r, j0, j1);
         E = mv_sum16(inl ? w * e2 : 0.0);
         if (it == 0) E0 = E;
         if (it == g.refine) break;
@@ -291,7 +235,7 @@ __global__ __launch_bounds__(kMvThreads) void mv_triangulate_kernel(const MvArgs
 #pragma unroll
         for (int k = 0; k < 3; ++k) t3[k] = mv_sum16(inl ? w * (j0[k] * r[0] + j1[k] * r[1]) : 0.0);
         double dX[3];
-        mv_solve3(A, t3, dX);
+        cam_solve3(A, t3, dX);
 #pragma unroll
         for (int k = 0; k < 3; ++k) X[k] -= dX[k];
     }
@@ -303,7 +247,7 @@ __global__ __launch_bounds__(kMvThreads) void mv_triangulate_kernel(const MvArgs
     double sigma;
     {
         double r[2], j0[3], j1[3];
-        mv_residual<true>(cam, X, a, b, r, j0, j1);
+        cam_residual<true>(cam, X, a, b, r, j0, j1);
         A[0] = mv_sum16(inl ? j0[0] * j0[0] + j1[0] * j1[0] : 0.0);
         A[1] = mv_sum16(inl ? j0[0] * j0[1] + j1[0] * j1[1] : 0.0);
         A[2] = mv_sum16(inl ? j0[0] * j0[2] + j1[0] * j1[2] : 0.0);
@@ -312,7 +256,8 @@ __global__ __launch_bounds__(kMvThreads) void mv_triangulate_kernel(const MvArgs
         A[5] = mv_sum16(inl ? j0[2] * j0[2] + j1[2] * j1[2] : 0.0);
         t3[0] = t3[1] = t3[2] = 0.0;
         double unused[3];
-        sigma = sqrt(mv_solve3(A, t3, unused));
+        const CamSolve3 q = cam_solve3(A, t3, unused);
+        sigma = sqrt(q.cof_trace / q.det);                 // trace(A^-1)
     }
 
     // ---- rule 5
@@ -341,17 +286,17 @@ __global__ __launch_bounds__(256) void mv_residuals_kernel(const double* __restr
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const long long p = i % P;
-    const double* cam = cams + (size_t)(i / P) * kMvCam;
+    const double* cam = cams + (size_t)(i / P) * kCamRow;
     const double x = (double)kp[i * 3], y = (double)kp[i * 3 + 1], c = (double)kp[i * 3 + 2];
     const double X0 = joints[p * 3], X1 = joints[p * 3 + 1], X2 = joints[p * 3 + 2];
     double out = (double)NAN;
-    if (mv_observed(x, y, c, conf_min) && isfinite(X0) && isfinite(X1) && isfinite(X2)) {
-        const double xc = cam[0] * X0 + cam[1] * X1 + cam[2] * X2 + cam[9];
-        const double yc = cam[3] * X0 + cam[4] * X1 + cam[5] * X2 + cam[10];
-        const double zc = cam[6] * X0 + cam[7] * X1 + cam[8] * X2 + cam[11];
-        if (zc > 0.0) {
+    if (cam_observed(x, y, c, conf_min) && isfinite(X0) && isfinite(X1) && isfinite(X2)) {
+        const double X[3] = {X0, X1, X2};
+        double Xc[3];
+        cam_to_view(cam, X, Xc);
+        if (Xc[2] > 0.0) {
             const double k1 = cam[16], k2 = cam[17], p1 = cam[18], p2 = cam[19], k3 = cam[20];
-            const double u = xc / zc, v = yc / zc, r2 = u * u + v * v;
+            const double u = Xc[0] / Xc[2], v = Xc[1] / Xc[2], r2 = u * u + v * v;
             const double gr = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2;
             const double ud = u * gr + 2.0 * p1 * u * v + p2 * (r2 + 2.0 * u * u);
             const double vd = v * gr + p1 * (r2 + 2.0 * v * v) + 2.0 * p2 * u * v;

@@ -27,8 +27,8 @@ and `ridge` are chosen on the synthetic body with the float64 restatement, not f
 from __future__ import annotations
 
 import argparse
+import functools
 import json
-import os
 import sys
 
 import numpy as np
@@ -76,11 +76,7 @@ class FitResult:
 
 
 # ---- the kernels' wrappers -----------------------------------------------------------------------------------------------------
-def _hip(x, name):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f'{name}: the fit kernels take torch tensors on a HIP device, got {type(x).__name__}')
-    _lib.require_hip(x)
-    return x
+_hip = functools.partial(_lib.hip_tensor, kernels='the fit kernels take')
 
 
 def _observations(targets, conf):
@@ -97,12 +93,7 @@ def _observations(targets, conf):
 
 
 def _rows(x, name, N):
-    if x is None:
-        return None
-    x = _hip(x, name).detach().double().contiguous()
-    if tuple(x.shape) != (N, NX):
-        raise ValueError(f'{name} must be [{N}, 69], got {list(x.shape)}')
-    return x
+    return _lib.hip_rows(x, name, (N, NX), kernels='the fit kernels take')
 
 
 def fit_pose(nat, targets, conf, betas, init=None, prev=None, w_prior=None, w_smooth=0.0, iters=20, min_joints=6, want_normal=False):
@@ -262,13 +253,6 @@ def fit_joints(joints, conf=None, betas=None, times=None, fit_shape=False, shape
 
 
 # ---- skeleton file -> track ---------------------------------------------------------------------------------------------------------
-def _skeleton_dict(skeleton):
-    if isinstance(skeleton, (str, os.PathLike)):
-        with np.load(skeleton, allow_pickle=False) as f:
-            return {k: f[k] for k in f.files}
-    return dict(skeleton)
-
-
 def read_skeleton(skeleton):
     """Validate a skeleton (an .npz path or a dict) -> (joints [N,22,3] float32, conf [N,22] float32 or None, betas [10] or None,
     times [N] float64, the pass-through entries).  Required: joints_3d [N,22,3] (SMPL order) or [N,25,3] (BODY_25, mapped through
@@ -276,7 +260,7 @@ def read_skeleton(skeleton):
     exactly one of fps and times.  Optional: joint_conf [N,22|25], betas [10] and the track's own
     optional entries (`PASS_THROUGH`), which are handed on untouched.  Any other key is refused by name."""
     from .data_loaders.dataloader_video import OPENPOSE_TO_SMPL
-    d = _skeleton_dict(skeleton)
+    d = _lib.npz_dict(skeleton)
     unknown = sorted(set(d) - set(SKELETON_KEYS) - set(PASS_THROUGH))
     if unknown:
         raise ValueError(f'skeleton: unknown keys {unknown}; a skeleton has {list(SKELETON_KEYS)} and may carry {list(PASS_THROUGH)}')
@@ -318,7 +302,7 @@ def fit_track(skeleton, body_model='body_models/smplx_model', device='cuda:0', r
     """A skeleton (`read_skeleton`) -> a track dict with only `TRACK_KEYS`: the fitted global_orient [N,3], transl [N,3],
     body_pose [N,63], betas [10] (float32) and valid [N], fps or times as given, and the skeleton's pass-through entries.  With
     cam2world among them `read_track` accepts it; without, `floor.calibrate_track` does.  `kw` goes to `fit_joints`."""
-    d = _skeleton_dict(skeleton)
+    d = _lib.npz_dict(skeleton)
     joints, conf, betas, times, extra = read_skeleton(d)
     res = fit_joints(joints, conf=conf, betas=betas, times=times, body_model=body_model, device=device, **kw)
     p = res.params.astype(np.float32)

@@ -42,6 +42,7 @@ several views, 10 cm at the same, 2.7 cm at a tenth)."""
 from __future__ import annotations
 
 import argparse
+import functools
 import json
 import sys
 
@@ -84,20 +85,11 @@ class FitViewsResult:
 
 
 # ---- the kernel's wrapper ------------------------------------------------------------------------------------------------------
-def _hip(x, name):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f'{name}: the fit_views kernel takes torch tensors on a HIP device, got {type(x).__name__}')
-    _lib.require_hip(x)
-    return x
+_hip = functools.partial(_lib.hip_tensor, kernels='the fit_views kernel takes')
 
 
 def _rows(x, name, N):
-    if x is None:
-        return None
-    x = _hip(x, name).detach().double().contiguous()
-    if tuple(x.shape) != (N, NX):
-        raise ValueError(f'{name} must be [{N}, 69], got {list(x.shape)}')
-    return x
+    return _lib.hip_rows(x, name, (N, NX), kernels='the fit_views kernel takes')
 
 
 def fit_views_pose(nat, keypoints, cams, betas, init, prev=None, w_prior=None, w_smooth=0.0, w_smooth_t=0.0, sigma_px=0.0, conf_min=CONF_MIN,

@@ -25,8 +25,8 @@ assumes."""
 from __future__ import annotations
 
 import argparse
+import functools
 import json
-import os
 import sys
 
 import numpy as np
@@ -182,11 +182,7 @@ def compare_planes(est, cam2world, up_axis, floor_height=None):
 
 
 # ---- the kernels' wrappers -----------------------------------------------------------------------------------------------------
-def _hip(x, name):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f'{name}: the floor kernels take torch tensors on a HIP device, got {type(x).__name__}')
-    _lib.require_hip(x)
-    return x
+_hip = functools.partial(_lib.hip_tensor, kernels='the floor kernels take')
 
 
 def floor_candidates(joints, times, valid_idx, keypoints=None, conf_min=0.2, v_max=0.10, max_gap=0.05):
@@ -318,13 +314,6 @@ def check_floor(joints_cam, cam2world, up_axis, floor_height=None, **kw):
     return est, angle, diff
 
 
-def _track_dict(track):
-    if isinstance(track, (str, os.PathLike)):
-        with np.load(track, allow_pickle=False) as f:
-            return {k: f[k] for k in f.files}
-    return dict(track)
-
-
 def track_joints(track, body_model, device='cuda:0'):
     """(raw dict, `read_track`'s rec, joints [N,22,3] float32 in the camera frame on the device) of a track whose cam2world is
     optional: `read_track` validates a copy with a placeholder identity, so its refusals stay the single source of truth."""
@@ -332,7 +321,7 @@ def track_joints(track, body_model, device='cuda:0'):
     from .data_loaders.dataloader_video import _body_model
     from .data_loaders.track import read_track
     from .export import _joints
-    d = _track_dict(track)
+    d = _lib.npz_dict(track)
     probe = dict(d)
     probe.setdefault('cam2world', np.eye(4))
     rec = read_track(probe)
@@ -392,7 +381,7 @@ def main(argv=None):
     if not args.check and not args.out:
         raise SystemExit('give --out calibrated.npz (or --check)')
     kw = {name: getattr(args, name) for name, _, _, _ in OPTIONS}
-    raw = _track_dict(args.track)
+    raw = _lib.npz_dict(args.track)
     if args.check and 'cam2world' not in raw:
         raise SystemExit(f'{args.track}: --check compares the track\'s cam2world with the estimate, and it has none')
     try:

@@ -27,8 +27,8 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
+import functools
 import json
-import os
 import sys
 
 import numpy as np
@@ -63,11 +63,7 @@ class Triangulation:
 
 
 # ---- the kernels' wrappers -----------------------------------------------------------------------------------------------------
-def _hip(x, name):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f'{name}: the multiview kernels take torch tensors on a HIP device, got {type(x).__name__}')
-    _lib.require_hip(x)
-    return x
+_hip = functools.partial(_lib.hip_tensor, kernels='the multiview kernels take')
 
 
 def _operands(keypoints, cams):
@@ -151,13 +147,6 @@ def pack_cameras(camera_mtx, world2cam, dist_coeffs=None):
     return cams
 
 
-def _views_dict(views):
-    if isinstance(views, (str, os.PathLike)):
-        with np.load(views, allow_pickle=False) as f:
-            return {k: f[k] for k in f.files}
-    return dict(views)
-
-
 def read_views(views, min_views=2):
     """Validate a views file (an .npz path or a dict) -> a dict with keypoints [V,N,K,3] float32 (K 22 or 25), camera_mtx
     [V,3,3], world2cam [V,4,4] (the inverse of cam2world where that was given), dist_coeffs [V,5] or None, world_up_axis 'z' |
@@ -165,7 +154,7 @@ def read_views(views, min_views=2):
     where given.  Required: keypoints_2d, camera_mtx, exactly one of world2cam and cam2world, exactly one of fps and times.  Any
     key outside `VIEW_KEYS` is refused by name.  `min_views`: the fewest views accepted (triangulation needs two; `rohm_amd.fit_views`
     reads a file with one)."""
-    d = _views_dict(views)
+    d = _lib.npz_dict(views)
     unknown = sorted(set(d) - set(VIEW_KEYS))
     if unknown:
         raise ValueError(f'views: unknown keys {unknown}; a views file has {list(VIEW_KEYS)}')

@@ -6,32 +6,13 @@ header to the letter; only the order of the sums differs from the kernel's.
 
 `torch_fit_pose` / `torch_shape_moments` wrap the two with the signatures of `rohm_amd.fit.fit_pose` / `shape_moments` on CPU
 tensors, so that a test without a GPU can run `fit_joints` and `fit_track` on them."""
-import json
-import os
-
 import numpy as np
+
+import helpers
 
 NJ, NX, NROT = 22, 69, 66
 LAMBDA0, LAMBDA_MIN, LAMBDA_MAX, TRIES, DIAG_EPS, DEGENERATE = 1e-3, 1e-9, 1e8, 8, 1e-9, 1e-9
-_PARITY = {}
-
-
-def record(group, key, value):
-    """Keep the largest measured value of a session under profiles/fit_parity.json [group][key]."""
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'fit_parity.json')
-    _PARITY[group, key] = max(float(value), _PARITY.get((group, key), 0.0))
-    try:
-        with open(path) as f:
-            data = json.load(f)
-    except (OSError, ValueError):
-        data = {}
-    data.setdefault(group, {})[key] = _PARITY[group, key]
-    try:
-        with open(path, 'w') as f:
-            json.dump(data, f, indent=1, sort_keys=True)
-            f.write('\n')
-    except OSError:
-        pass
+record = helpers.parity_recorder('fit_parity.json')
 
 
 def _f32(a):

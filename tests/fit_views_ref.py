@@ -6,35 +6,15 @@ are tests/fit_ref.py's, the undistortion is tests/multiview_ref.py's; only the o
 
 `torch_fit_views_pose` wraps it with the signature of `rohm_amd.fit_views.fit_views_pose` on CPU tensors.  The makers of rigs and
 frames for the tests are at the end."""
-import json
-import os
-
 import numpy as np
 
 import fit_ref as FR
+import helpers
 import multiview_ref as MR
 
 NJ, NX, NROT, CAM, MAX_VIEWS, NREPORT = FR.NJ, FR.NX, FR.NROT, MR.CAM, 16, 8
 SINGULAR = 1e-12
-_PARITY = {}
-
-
-def record(group, key, value):
-    """Keep the largest measured value of a session under profiles/fit_views_parity.json [group][key]."""
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'fit_views_parity.json')
-    _PARITY[group, key] = max(float(value), _PARITY.get((group, key), 0.0))
-    try:
-        with open(path) as f:
-            data = json.load(f)
-    except (OSError, ValueError):
-        data = {}
-    data.setdefault(group, {})[key] = _PARITY[group, key]
-    try:
-        with open(path, 'w') as f:
-            json.dump(data, f, indent=1, sort_keys=True)
-            f.write('\n')
-    except OSError:
-        pass
+record = helpers.parity_recorder('fit_views_parity.json')
 
 
 # ---- the pieces of the rule ---------------------------------------------------------------------------------------------------

@@ -3,32 +3,13 @@
 hand-computable cases in tests/test_floor_ref.py.  The rules are stated in include/rohm_hip.h and in rohm_amd/floor.py.  Inputs
 are taken as float32 (what the kernels read) and every operation is float64.  The refinement and the camera pose are written
 out again here, not imported; only `FloorEstimate` and the refusals (`check_candidates`, `check_estimate`) are the module's."""
-import json
-import os
-
 import numpy as np
+
+import helpers
 
 TOES = (10, 11)
 SIGMA = 0.005                    # the noise of the noisy planted floor: 5 mm
-_PARITY = {}
-
-
-def record(group, key, value):
-    """Keep the largest measured value of a session under profiles/floor_parity.json [group][key]."""
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'floor_parity.json')
-    _PARITY[group, key] = max(float(value), _PARITY.get((group, key), 0.0))
-    try:
-        with open(path) as f:
-            data = json.load(f)
-    except (OSError, ValueError):
-        data = {}
-    data.setdefault(group, {})[key] = _PARITY[group, key]
-    try:
-        with open(path, 'w') as f:
-            json.dump(data, f, indent=1, sort_keys=True)
-            f.write('\n')
-    except OSError:
-        pass
+record = helpers.parity_recorder('floor_parity.json')
 DEGENERATE = 1e-9
 INT64_MIN = np.iinfo(np.int64).min
 UP = {'z': 2, 'y': 1}

@@ -1,4 +1,5 @@
 """Shared test helpers (seeded inputs identical to oracle/make_golden.py)."""
+import json
 import os
 
 import numpy as np
@@ -14,6 +15,28 @@ def seeded(seed, *shape):
 
 def golden(name):
     return np.load(os.path.join(GOLDEN, name))
+
+
+def parity_recorder(file_name):
+    """-> record(group, key, value): keeps the largest value measured in a session under profiles/<file_name> [group][key]."""
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', file_name)
+    largest = {}
+
+    def record(group, key, value):
+        largest[group, key] = max(float(value), largest.get((group, key), 0.0))
+        try:
+            with open(path) as f:
+                data = json.load(f)
+        except (OSError, ValueError):
+            data = {}
+        data.setdefault(group, {})[key] = largest[group, key]
+        try:
+            with open(path, 'w') as f:
+                json.dump(data, f, indent=1, sort_keys=True)
+                f.write('\n')
+        except OSError:
+            pass
+    return record
 
 
 def cpu_noise_sequence(torch_seed, shape, steps, trajnet_layout=False):

@@ -11,31 +11,12 @@ best other candidate with the same count (infinite where there is none).
 
 `torch_triangulate` / `torch_view_residuals` wrap the two with the signatures of `rohm_amd.multiview.triangulate` /
 `view_residuals` on CPU tensors, so that a test without a GPU can run `triangulate_views` on them."""
-import json
-import os
-
 import numpy as np
 
+import helpers
+
 MAX_VIEWS, MAX_PAIRS, CAM = 16, 120, 24
-_PARITY = {}
-
-
-def record(group, key, value):
-    """Keep the largest measured value of a session under profiles/multiview_parity.json [group][key]."""
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'multiview_parity.json')
-    _PARITY[group, key] = max(float(value), _PARITY.get((group, key), 0.0))
-    try:
-        with open(path) as f:
-            data = json.load(f)
-    except (OSError, ValueError):
-        data = {}
-    data.setdefault(group, {})[key] = _PARITY[group, key]
-    try:
-        with open(path, 'w') as f:
-            json.dump(data, f, indent=1, sort_keys=True)
-            f.write('\n')
-    except OSError:
-        pass
+record = helpers.parity_recorder('multiview_parity.json')
 
 
 # ---- the pieces of the rule ---------------------------------------------------------------------------------------------------
