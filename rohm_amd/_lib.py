@@ -259,6 +259,16 @@ SIGNATURES_FIT_VIEWS = {
     'rohm_fit_views_pose': (C.c_int, [C.c_void_p] * 7 + [C.c_double] * 4 + [C.c_int] * 4 + [C.c_void_p] * 5),
 }
 
+# the same for include/rohm_rig.h
+SIGNATURES_RIG = {
+    'rohm_rig_pair_ws_bytes': (C.c_longlong, [C.c_int, C.c_longlong]),
+    'rohm_rig_ba_ws_bytes': (C.c_longlong, [C.c_int, C.c_longlong]),
+    'rohm_rig_pair_hypotheses': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_double] * 2 + [C.c_void_p] * 5),
+    'rohm_rig_pair_moments': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_double] * 2 + [C.c_void_p] * 3),
+    'rohm_rig_ba_moments': (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_double] * 3 + [C.c_void_p] * 5),
+    'rohm_rig_ba_update': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_double] * 3 + [C.c_void_p] * 3),
+}
+
 
 def lib():
     """Load (once) and return the ctypes library; raises if it has not been built."""
@@ -272,7 +282,8 @@ def lib():
         # the shipped library must export every declared symbol; an experiment library selected through ROHM_HIP_LIB (same-box A/B
         # runs against an older tree, scripts/build_variant.py) may lack the newest ones -- they then fail where they are used
         strict = not os.environ.get('ROHM_HIP_LIB')
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_MULTIVIEW.items()) + list(SIGNATURES_FIT_VIEWS.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_MULTIVIEW.items()) + list(SIGNATURES_FIT_VIEWS.items()) + \
+                list(SIGNATURES_RIG.items()):
             if not strict and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)
