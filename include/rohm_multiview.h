@@ -9,7 +9,8 @@
  * goes on the caller-supplied stream with no synchronisation, no allocation and no read-back, so every stream-taking
  * function here may be recorded into a hipGraph (device operands are read at replay time, the scalars travel in the kernel
  * arguments); outputs may hold anything on entry and are written wholly; an optional output passed as NULL is not computed.
- * tests/test_gpu_multiview_contract.py holds the functions of this header to those contracts.
+ * tests/test_gpu_stale_memory.py, test_gpu_bounds.py, test_gpu_stream_order.py and test_gpu_graph_replay.py hold the functions
+ * of this header to those contracts, with the cases of tests/header_cases.py.
  *
  * Cameras.  cams [V,24] float64, one row per view: R (9 values, row-major, world -> camera: x_cam = R X + t), t (3), fx, fy,
  * cx, cy, k1, k2, p1, p2, k3, three zeros.  2 <= V <= 16 (rohm_mv_limits).  No atomics; every sum is taken in a fixed order:

@@ -11,7 +11,8 @@
  * function here may be recorded into a hipGraph (device operands are read at replay time, the scalars travel in the kernel
  * arguments); outputs may hold anything on entry and are written wholly; a workspace may hold anything on entry and holds
  * nothing a later call needs; an optional output passed as NULL is not computed.
- * tests/test_gpu_rig_contract.py holds the functions of this header to those contracts.
+ * tests/test_gpu_stale_memory.py, test_gpu_bounds.py, test_gpu_stream_order.py and test_gpu_graph_replay.py hold the functions
+ * of this header to those contracts, with the cases of tests/header_cases.py.
  *
  * Cameras.  cams [V,24] float64 are the rows of rohm_multiview.h: R (9, row-major, world -> camera), t (3), fx, fy, cx, cy, k1,
  * k2, p1, p2, k3, three zeros; 2 <= V <= 16.  The pair functions read only the intrinsics (values 12..20).  keypoints [V,N,J,3]

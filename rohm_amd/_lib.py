@@ -1,4 +1,4 @@
-"""ctypes binding of librohm_hip.so (the C ABI in include/rohm_hip.h).
+"""ctypes binding of librohm_hip.so (the C ABI in include/rohm_hip.h and the headers that include it: `HEADERS`).
 
 There is no CPU fallback: if the library is missing, or a tensor is not on a HIP device,
 the call raises.  Build the library with `python -m rohm_amd.build`.
@@ -68,7 +68,10 @@ class ProfileRow(C.Structure):
 
 _lib = None
 
-# name -> (restype, argtypes); must list every symbol declared in include/rohm_hip.h
+# the public headers under include/; together they declare every symbol of the library, each in one header
+HEADERS = ('rohm_hip.h', 'rohm_multiview.h', 'rohm_fit_views.h', 'rohm_rig.h')
+
+# name -> (restype, argtypes); must list every symbol the HEADERS declare (rohm_hip.h's first, then header by header)
 SIGNATURES = {
     'rohm_last_error': (C.c_char_p, []),
     'rohm_version': (C.c_int, []),
@@ -245,22 +248,13 @@ SIGNATURES = {
     'rohm_floor_moments': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     'rohm_fit_pose': (C.c_int, [C.c_void_p] * 7 + [C.c_double, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4),
     'rohm_fit_shape_moments': (C.c_int, [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3),
-}
-
-# the same for include/rohm_multiview.h
-SIGNATURES_MULTIVIEW = {
+    # include/rohm_multiview.h
     'rohm_mv_limits': (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'rohm_mv_triangulate': (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_double] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 6),
     'rohm_mv_residuals': (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_double, C.c_void_p, C.c_void_p]),
-}
-
-# the same for include/rohm_fit_views.h
-SIGNATURES_FIT_VIEWS = {
+    # include/rohm_fit_views.h
     'rohm_fit_views_pose': (C.c_int, [C.c_void_p] * 7 + [C.c_double] * 4 + [C.c_int] * 4 + [C.c_void_p] * 5),
-}
-
-# the same for include/rohm_rig.h
-SIGNATURES_RIG = {
+    # include/rohm_rig.h
     'rohm_rig_pair_ws_bytes': (C.c_longlong, [C.c_int, C.c_longlong]),
     'rohm_rig_ba_ws_bytes': (C.c_longlong, [C.c_int, C.c_longlong]),
     'rohm_rig_pair_hypotheses': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_double] * 2 + [C.c_void_p] * 5),
@@ -282,8 +276,7 @@ def lib():
         # the shipped library must export every declared symbol; an experiment library selected through ROHM_HIP_LIB (same-box A/B
         # runs against an older tree, scripts/build_variant.py) may lack the newest ones -- they then fail where they are used
         strict = not os.environ.get('ROHM_HIP_LIB')
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_MULTIVIEW.items()) + list(SIGNATURES_FIT_VIEWS.items()) + \
-                list(SIGNATURES_RIG.items()):
+        for name, (res, args) in SIGNATURES.items():
             if not strict and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)

@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE ONLY (host side of tests/test_gpu_graph_replay.py): static input slots, the rewrite of host arrays with other
 VALID values, a call log that notes whether each call was made while its stream was recording, the record / replay protocol, and
-the three tables that say what becomes of every stream-taking entry point of include/rohm_hip.h under a graph capture.  Nothing in
+the three tables that say what becomes of every stream-taking entry point of the public headers under a graph capture.  Nothing in
 rohm_amd/ imports this module; it has no GPU code of its own.
 
 include/rohm_hip.h ("Conventions", recordable calls) promises that a call on a recording stream replays as the same call made again
@@ -62,6 +62,9 @@ REPLAYED = {
     'rohm_amass_metrics': 'metrics', 'rohm_scene_metrics': 'metrics', 'rohm_result_rows': 'metrics', 'rohm_traj_report': 'metrics',
     'rohm_track_quality': 'track', 'rohm_floor_clearance': 'track', 'rohm_floor_candidates': 'track', 'rohm_floor_moments': 'track',
     'rohm_fit_pose': 'track', 'rohm_fit_shape_moments': 'track',
+    'rohm_mv_triangulate': 'multiview', 'rohm_mv_residuals': 'multiview',
+    'rohm_fit_views_pose': 'fit_views',
+    'rohm_rig_pair_hypotheses': 'rig', 'rohm_rig_pair_moments': 'rig', 'rohm_rig_ba_moments': 'rig', 'rohm_rig_ba_update': 'rig',
 }
 
 # entry point -> the header sentence that says it waits (looked up in stream_order.header_prose by the host test)
@@ -218,15 +221,6 @@ def record(fn, stream, lib_obj=None, stream_at=None, poison=True):
 
 
 # ---- the protocol --------------------------------------------------------------------------------------------------------------
-def snapshot(out):
-    return [(label, t.detach().clone()) for label, t in out]
-
-
-def differences(got, want):
-    assert [l for l, _ in got] == [l for l, _ in want], ([l for l, _ in got], [l for l, _ in want])
-    return [(label, d) for (label, a), (_, b) in zip(got, want) for d in [SM.first_difference(a, b)] if d is not None]
-
-
 def poison_tensors(tensors):
     for t in tensors:
         SM.fill_bytes(t, ONES)
@@ -250,16 +244,16 @@ def run_case(slots, call, host, rewrite, side, claims, inplace=False, buffers=la
         slots.load(1)
         call(slots, host())                                      # the warm-up (caches, lazily created streams, first-call probes)
         slots.load(1)
-        e1 = snapshot(call(slots, host()))
+        e1 = SM.snapshot(call(slots, host()))
         slots.load(2)
-        e2 = snapshot(call(slots, host()))
+        e2 = SM.snapshot(call(slots, host()))
         e11 = None
         if inplace:
             slots.load(1)
             call(slots, host())
-            e11 = snapshot(call(slots, host()))
+            e11 = SM.snapshot(call(slots, host()))
         side.synchronize()
-        assert differences(e1, e2), 'the two value sets give the same outputs: the case could not tell a stale input'
+        assert SM.differences(e1, e2), 'the two value sets give the same outputs: the case could not tell a stale input'
         slots.load(1)
     side.synchronize()
     h = host()
@@ -278,16 +272,16 @@ def run_case(slots, call, host, rewrite, side, claims, inplace=False, buffers=la
             slots.load(k)
             for _ in range(times):
                 graph.replay()
-            got = snapshot(out)
+            got = SM.snapshot(out)
             side.synchronize()
-            diff = differences(got, want)
+            diff = SM.differences(got, want)
             assert not diff, f'{what}: the replay differs from the eager call: {diff[:3]} (output, (first differing element, replay, eager))'
             return got
         slots.load(1)
         graph.replay()                                           # check 3: nothing poisoned yet beyond what the graph itself fills
-        got = snapshot(out)
+        got = SM.snapshot(out)
         side.synchronize()
-        diff = differences(got, e1)
+        diff = SM.differences(got, e1)
         assert not diff, f'first replay: differs from the eager call on set 1: {diff[:3]}'
         replay_and_compare(2, e2, 'replay on value set 2')
         final = replay_and_compare(1, e1, 'replay on value set 1 again')

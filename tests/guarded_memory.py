@@ -8,8 +8,9 @@ neighbouring tensor, and a load there returns finite leftovers: nothing notices.
   * `guard()` replaces torch.empty, torch.empty_like, Tensor.new_empty, torch.zeros and Tensor.new_zeros: what they return is a view into
     the middle of a larger flat uint8 buffer -- BAND bytes of 0xFF (fp32 / fp64 NaN, integer -1) in front, the zero-filled interior,
     then 0xFF padding up to the next multiple of 512 bytes and BAND more bytes of 0xFF.  The view has the dtype and shape that were
-    asked for and a 512-byte-aligned address.  A store outside the interior changes a band byte (`violations()`); a load there is NaN and
-    shows in the result.
+    asked for and a 512-byte-aligned address -- or, with `guard(offset=True)`, an address one element of its own dtype past such a
+    boundary, the least alignment the headers promise to accept.  A store outside the interior changes a band byte (`violations()`);
+    a load there is NaN and shows in the result.
   * `place(t, placement)` puts an INPUT tensor into a flat device buffer of 0xFF bytes with BAND bytes on either side (`Canvas`), so a
     read past an input is NaN as well and a write to an input is seen (`untouched()`).
 
@@ -78,8 +79,8 @@ class Guard:
     """The state of one `guard()`: `records` (every served allocation, in order), `served`, `unguarded` (the number of allocations passed
     through to torch unchanged) and `passed_through` (what they were)."""
 
-    def __init__(self, device_types):
-        self.device_types = tuple(device_types)
+    def __init__(self, device_types, offset=False):
+        self.device_types, self.offset = tuple(device_types), bool(offset)
         self.records = []
         self.passed_through = []
         self._by_storage = {}
@@ -102,12 +103,14 @@ class Guard:
 
     def serve(self, kind, shape, dtype, device, strides=None, requires_grad=False):
         nbytes = _numel(shape) * _itemsize(dtype)
-        flat, front = _flat(nbytes, device)
+        lead = _itemsize(dtype) if self.offset else 0
+        flat, front = _flat(lead + nbytes, device)
+        front += lead
         inner = flat[front:front + nbytes]
         inner.zero_()
         typed = inner.view(dtype)
         out = typed.view(shape) if strides is None else typed.as_strided(shape, strides)
-        assert out.data_ptr() % ALIGN == 0 or nbytes == 0
+        assert out.data_ptr() % ALIGN == lead or nbytes == 0
         rec = _Record(kind, flat, front, nbytes, shape, dtype)
         self.records.append(rec)
         self._by_storage[flat.untyped_storage().data_ptr()] = rec
@@ -249,11 +252,12 @@ def install(monkeypatch, g):
 
 
 @contextlib.contextmanager
-def guard(device_types=('cuda',)):
+def guard(device_types=('cuda',), offset=False):
     """The guarded allocators as a context manager (its own MonkeyPatch, undone on exit) -> the `Guard`.  Every flat buffer stays alive
-    until exit (and as long as the Guard is), so no band is recycled while the case runs."""
+    until exit (and as long as the Guard is), so no band is recycled while the case runs.  `offset`: every allocation starts one
+    element of its own dtype past a 512-byte boundary instead of on it."""
     import pytest
-    g = Guard(device_types)
+    g = Guard(device_types, offset)
     with pytest.MonkeyPatch.context() as m:
         install(m, g)
         yield g
@@ -264,7 +268,8 @@ class Canvas:
     """A flat buffer of 0xFF bytes holding one input tensor (`view`) with BAND bytes on either side, and a copy of the whole buffer
     taken at placement.  placement 'aligned': the first element lies on a 512-byte boundary.  placement 'slice' ([B, 294, 1, T] float32
     only): the canvas holds B + 1 clips, the first of them all 0xFF on a 512-byte boundary, and the operand is clips 1 .. B -- what a
-    caller who passes `batch[1:]` hands in: 8 bytes past a 16-byte boundary for T = 143 and T = 63."""
+    caller who passes `batch[1:]` hands in: 8 bytes past a 16-byte boundary for T = 143 and T = 63.  placement 'offset': the first
+    element lies one element past a 512-byte boundary (4 bytes for float32, 8 for float64), the 0xFF element in front of it is band."""
 
     def __init__(self, t, placement='aligned', device=None, label=None, band=SM.PATTERNS['ones']):
         """`band`: the 4-byte word the bytes around the operand repeat (little-endian).  The default is all-ones; a test that must
@@ -280,6 +285,8 @@ class Canvas:
             if t.dim() != 4 or t.shape[1] != 294 or t.shape[2] != 1 or t.dtype != torch.float32:
                 raise ValueError(f"placement 'slice' is for [B, 294, 1, T] float32 operands, got {t.dtype} {tuple(t.shape)}")
             lead = 294 * int(t.shape[3]) * 4
+        elif placement == 'offset':
+            lead = t.element_size()
         elif placement != 'aligned':
             raise ValueError(f'unknown placement {placement!r}')
         self.flat, front = _flat(lead + nbytes, device)

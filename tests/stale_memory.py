@@ -1,7 +1,8 @@
 """TEST INFRASTRUCTURE ONLY (host side of tests/test_gpu_stale_memory.py): the memory-poisoning replacement of torch's
-uninitialised allocators, bit-exact comparison, the parser that lists every entry point of include/rohm_hip.h taking a
-caller-owned buffer, and the coverage list that names the case(s) exercising each of them; for tests/test_gpu_bounds.py also the
-parser that lists every entry point with a pointer to numbers (`abi_pointer_functions`) and its exemptions.
+uninitialised allocators, bit-exact comparison (`snapshot`, `differences`: the one copy every family imports), the parser that lists
+every entry point of the public headers (rohm_amd._lib.HEADERS, read together) taking a caller-owned buffer, and the coverage list
+that names the case(s) exercising each of them; for tests/test_gpu_bounds.py also the parser that lists every entry point with a
+pointer to numbers (`abi_pointer_functions`) and its exemptions.
 
 include/rohm_hip.h ("Caller-owned memory") promises that `ws`, `scratch`, `saved` and output buffers may hold anything on
 entry.  Every Python wrapper gets them from torch.empty / empty_like / new_empty; `poison` replaces those three for the
@@ -106,23 +107,42 @@ def first_difference(a, b):
 
 
 # ---- the ABI's caller-owned buffers ------------------------------------------------------------------------------------------
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'rohm_hip.h')
+INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include')
+_HEADERS = {}
+
+
+def abi_headers():
+    """{file name: text} of every public header, in the order of rohm_amd._lib.HEADERS (read once)."""
+    if not _HEADERS:
+        from rohm_amd import _lib
+        for name in _lib.HEADERS:
+            with open(os.path.join(INCLUDE, name)) as f:
+                _HEADERS[name] = f.read()
+    return dict(_HEADERS)
+
+
+def abi_text():
+    return '\n'.join(abi_headers().values())
+
+
+def declarations(text=None):
+    """[(entry point, [the text of each parameter])] of every `rohm_*(...);` declaration outside a comment, in order; `text`
+    defaults to all public headers together."""
+    text = re.sub(r'/\*.*?\*/', ' ', abi_text() if text is None else text, flags=re.S)
+    text = re.sub(r'//[^\n]*', ' ', text)
+    return [(m.group(1), [p for p in m.group(2).split(',') if p.strip() not in ('', 'void')])
+            for m in re.finditer(r'\b(rohm_\w+)\s*\(([^;{}()]*)\)\s*;', text)]
 
 
 def abi_buffer_functions(text=None):
-    """{entry point: [buffer names]} for every declaration of include/rohm_hip.h with a `void* <name>, size_t <name>_bytes`
-    (or `size_t bytes`) parameter pair (const or not): the functions that are handed a caller-owned workspace."""
-    if text is None:
-        with open(HEADER) as f:
-            text = f.read()
-    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
-    text = re.sub(r'//[^\n]*', ' ', text)
+    """{entry point: [buffer names]} for every declaration with a `void* <name>, size_t <name>_bytes` (or `size_t bytes`) parameter
+    pair (const or not): the functions that are handed a caller-owned workspace."""
     out = {}
-    for m in re.finditer(r'\b(rohm_\w+)\s*\(([^;{}()]*)\)\s*;', text):
-        names = [p.group(1) for p in re.finditer(r'void\s*\*\s*(\w+)\s*,\s*size_t\s+(\w*?)_?bytes\b', m.group(2))
+    for name, params in declarations(text):
+        names = [p.group(1) for p in re.finditer(r'void\s*\*\s*(\w+)\s*,\s*size_t\s+(\w*?)_?bytes\b', ','.join(params))
                  if p.group(2) in (p.group(1), '')]
         if names:
-            out[m.group(1)] = names
+            out[name] = names
     return out
 
 
@@ -130,26 +150,33 @@ _POINTEE = r'(?:float|double|void|int|unsigned(?:\s+(?:char|int))?|long\s+long|s
 
 
 def abi_pointer_functions(text=None):
-    """{entry point: [parameter names]} for every declaration of include/rohm_hip.h with a parameter that points at numbers --
-    `float*`, `double*`, `void*`, an integer pointer, a table of such pointers (`float* const*`), const or not: every function that
-    can be handed a caller's tensor.  Pointers to structs, handles and strings are not listed.  The header does not say in its types
-    which of these live on the host (plans, limits, camera matrices): POINTER_EXEMPT names the host-only calls one by one, and
+    """{entry point: [parameter names]} for every declaration with a parameter that points at numbers -- `float*`, `double*`,
+    `void*`, an integer pointer, a table of such pointers (`float* const*`), const or not: every function that can be handed a
+    caller's tensor.  Pointers to structs, handles and strings are not listed.  The headers do not say in their types which of these
+    live on the host (plans, limits, camera matrices): POINTER_EXEMPT names the host-only calls one by one, and
     tests/test_guarded_memory_host.py holds every other function to a guarded-memory case."""
-    if text is None:
-        with open(HEADER) as f:
-            text = f.read()
-    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
-    text = re.sub(r'//[^\n]*', ' ', text)
     out = {}
-    for m in re.finditer(r'\b(rohm_\w+)\s*\(([^;{}()]*)\)\s*;', text):
+    for name, params in declarations(text):
         names = []
-        for param in m.group(2).split(','):
+        for param in params:
             p = re.match(r'^\s*(?:const\s+)?' + _POINTEE + r'\s*(?:const\s*)?\*\s*(?:const\s*\*\s*)?(?:const\s+)?(\w+)\s*$', param)
             if p:
                 names.append(p.group(1))
         if names:
-            out[m.group(1)] = names
+            out[name] = names
     return out
+
+
+# ---- one snapshot, one comparison ----------------------------------------------------------------------------------------------
+def snapshot(out):
+    """Clones of the tensors of [(label, tensor)], queued on the current stream (no wait)."""
+    return [(label, t.detach().clone()) for label, t in out]
+
+
+def differences(got, want):
+    """[(label, first_difference)] of the outputs that are not bit-identical; the two lists must carry the same labels."""
+    assert [l for l, _ in got] == [l for l, _ in want], ([l for l, _ in got], [l for l, _ in want])
+    return [(label, d) for (label, a), (_, b) in zip(got, want) for d in [first_difference(a, b)] if d is not None]
 
 
 # entry points with a pointer parameter that no guarded-memory case runs (tests/test_gpu_bounds.py), each with its reason
@@ -157,6 +184,7 @@ POINTER_EXEMPT = {
     'rohm_profile_stop': 'host-only: the row count goes to a host int, nothing on the device is touched',
     'rohm_output_process_plan': 'host-only: the launch plan is returned through two host ints',
     'rohm_adamw_limits': 'host-only: two host ints',
+    'rohm_mv_limits': 'host-only: two host ints',
     'rohm_smplx_create': 'create: copies the model arrays into device memory the handle owns, sized by V, J and n_shape_total',
     'rohm_smplx_set_skinning': 'create-time upload of the skinning arrays into memory the handle owns',
     'rohm_posenet_exchange_status': 'status call: reads the exchange header of a workspace a forward of the same shape wrote; it is run '
@@ -208,6 +236,9 @@ COVERAGE = {
     'train_helpers': ['rohm_train_cond', 'rohm_train_traj_window', 'rohm_q_sample', 'rohm_image_requantize', 'rohm_image_paste',
                       'rohm_image_overlay', 'rohm_image_flip_lr'],
     'optim': ['rohm_grad_norm', 'rohm_adamw_step'],
+    'multiview': ['rohm_mv_triangulate', 'rohm_mv_residuals'],
+    'fit_views': ['rohm_fit_views_pose'],
+    'rig': ['rohm_rig_pair_hypotheses', 'rohm_rig_pair_moments', 'rohm_rig_ba_moments', 'rohm_rig_ba_update'],
 }
 
 

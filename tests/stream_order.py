@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE ONLY (host side of tests/test_gpu_stream_order.py): a gate that holds one stream back, a call log over the
-loaded library, inputs whose values arrive behind the gate, the parser that lists every entry point of include/rohm_hip.h with a
+loaded library, inputs whose values arrive behind the gate, the parser that lists every entry point of the public headers with a
 `rohm_stream_t` parameter, and the two lists that say which of them may wait (SYNC_DOCUMENTED) or are not run (STREAM_EXEMPT).
 Nothing in rohm_amd/ imports this module.
 
@@ -35,31 +35,23 @@ ONES = SM.PATTERNS['ones']
 
 # ---- the ABI's stream parameters ---------------------------------------------------------------------------------------------
 def abi_stream_functions(text=None):
-    """{entry point: position of its `rohm_stream_t` parameter} for every declaration of include/rohm_hip.h that has one (next to
+    """{entry point: position of its `rohm_stream_t` parameter} for every declaration of the public headers that has one (next to
     stale_memory.abi_buffer_functions / abi_pointer_functions).  A declaration with two stream parameters is refused: the call log
     could not tell which one is the caller's."""
-    if text is None:
-        with open(SM.HEADER) as f:
-            text = f.read()
-    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
-    text = re.sub(r'//[^\n]*', ' ', text)
     out = {}
-    for m in re.finditer(r'\b(rohm_\w+)\s*\(([^;{}()]*)\)\s*;', text):
-        at = [i for i, param in enumerate(m.group(2).split(',')) if re.match(r'^\s*(?:const\s+)?rohm_stream_t\s+\w+\s*$', param)]
+    for name, params in SM.declarations(text):
+        at = [i for i, param in enumerate(params) if re.match(r'^\s*(?:const\s+)?rohm_stream_t\s+\w+\s*$', param)]
         if len(at) > 1:
-            raise ValueError(f'{m.group(1)} has {len(at)} rohm_stream_t parameters')
+            raise ValueError(f'{name} has {len(at)} rohm_stream_t parameters')
         if at:
-            out[m.group(1)] = at[0]
+            out[name] = at[0]
     return out
 
 
 def header_prose(text=None):
-    """The header as one line of text: comment decoration (` * ` at the start of a line) and line breaks become single spaces, so a
+    """The public headers as one line of text: comment decoration (` * ` at the start of a line) and line breaks become single spaces, so a
     sentence that the header wraps can be looked up as written."""
-    if text is None:
-        with open(SM.HEADER) as f:
-            text = f.read()
-    text = re.sub(r'\n\s*\*(?!/)', ' ', text)
+    text = re.sub(r'\n\s*\*(?!/)', ' ', SM.abi_text() if text is None else text)
     return re.sub(r'\s+', ' ', text)
 
 

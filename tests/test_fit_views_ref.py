@@ -1,9 +1,7 @@
 """CPU: the float64 restatement of `rohm_fit_views_pose` (tests/fit_views_ref.py) held to what does not depend on it -- central
 finite differences, the explicitly stacked Jacobian, a planted translation, multiview_ref's undistortion, a symmetry of the pinhole
-camera and planted bodies -- plus the statuses, the argument checks of the entry point (they come before any launch) and the
-header against the ctypes table and the built library.  tests/test_gpu_fit_views.py then holds the kernel to the restatement."""
-import os
-import re
+camera and planted bodies -- plus the statuses and the argument checks of the entry point (they come before any launch).
+tests/test_gpu_fit_views.py then holds the kernel to the restatement."""
 
 import numpy as np
 import pytest
@@ -207,24 +205,6 @@ def test_argument_errors_name_the_argument():
         assert call(**kw) == -1, kw
         assert word in L.rohm_last_error().decode(), (kw, L.rohm_last_error())
     assert call(N=0, h=None, kp=None, cams=None, betas=None, init=None, wp=None, params=None, report=None) == 0
-
-
-def test_abi_table_matches_the_header():
-    """include/rohm_fit_views.h against `_lib.SIGNATURES_FIT_VIEWS` and the built library, as tests/test_multiview_ref.py holds its
-    header: the same declared set, every symbol exported, as many ctypes arguments as parameters."""
-    from rohm_amd import _lib
-    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'rohm_fit_views.h')) as f:
-        raw = f.read()
-    text = re.sub(r'/\*.*?\*/', ' ', raw, flags=re.S)
-    declared = {m.group(1): [p for p in m.group(2).split(',') if p.strip() and p.strip() != 'void'] for m in re.finditer(r'\b(rohm_\w+)\s*\(([^;{}()]*)\)\s*;', text)}
-    assert set(declared) == set(_lib.SIGNATURES_FIT_VIEWS) == {'rohm_fit_views_pose'}
-    assert not set(_lib.SIGNATURES_FIT_VIEWS) & (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_MULTIVIEW))
-    L = _lib.lib()
-    for name, (res, args) in _lib.SIGNATURES_FIT_VIEWS.items():
-        fn = getattr(L, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args) and len(args) == len(declared[name]), name
-    assert '#include "rohm_hip.h"' in text
-    assert 'obey rohm_hip.h\'s "Conventions" and "Caller-owned memory" word for word' in re.sub(r'\s+', ' ', re.sub(r'\n\s*\*(?!/)', ' ', raw))
 
 
 # ---- recovery ----------------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,7 @@ function says (include/rohm_hip.h, "Conventions").
 
 tests/test_gpu_stale_memory.py poisons what a buffer HOLDS; tightly sized tensors still hide an access one row past a buffer (it
 lands in the caching allocator's rounding or in a neighbour and reads finite leftovers).  Here every case of that module's registry
-(imported, not copied: `G.CASES`, `G._run`, `G._differences`) and the cases of EXTRA below run once more
+(imported, not copied: `G.CASES`, `G._run`, `stale_memory.differences`) and the cases of EXTRA below run once more
 
   (a) under `guarded_memory.guard()`: every output, workspace, scratch and saved buffer the wrappers allocate lies between two 1 MiB
       bands of 0xFF.  No band byte may change, nothing may be allocated past the guard without a named reason, and the outputs equal
@@ -24,6 +24,11 @@ lands in the caching allocator's rounding or in a neighbour and reads finite lef
       finish_pack_kernel, the output heads, ddpm_step*, the training tile loads, traj_copy) or, in the stack form's closing phase,
       with 16-byte accesses declared 4-byte aligned (rows of T = 143 floats are never 16-byte aligned, slice or not), and reads the
       training parameters with 4-byte accesses.  The one exception was fixed here (Findings).
+  (d') for the three headers next to rohm_hip.h (multiview, fit_views, rig), whose opening comments promise that an operand "needs
+      the alignment of its element only": every input on an 'offset' canvas and every allocation from `guard(offset=True)`, so that
+      inputs, outputs and workspaces all start ONE ELEMENT past a 512-byte boundary (4 bytes for float32 / int32, 8 for float64 /
+      int64); results equal the aligned run bit for bit, canvases and bands untouched.  A further test counts, through the loaded
+      library, that each of these three cases calls every declaration of its header, the host-only ones included.
   (e) once with a planted overrun, to show the check can fail: `rohm_ddpm_step` with n four floats larger than its tensors, inputs on
       canvases, the output from the guarded allocator.  Every access stays inside the test's own allocations.
 
@@ -60,16 +65,20 @@ Findings:
     rohm_repr_stats_scratch_bytes, rohm_depth_workspace_bytes, rohm_color_workspace_bytes, rohm_grad_norm_scratch_bytes
     (rohm_clips_scratch_bytes is 0 at these clip lengths: nothing to hold; rohm_posenet_stack_timeline_bytes is not run).
 
-Sizes (MI355X): 83 cases (78 of the registry, 5 here), 324 guarded allocations in (a), 1153 canvases in (c); per family, cases /
+Sizes (MI355X): 86 cases (81 of the registry, 5 here), 352 guarded allocations in (a), 1170 canvases in (c); per family, cases /
 guarded allocations / canvases: amass 1 / 15 / 16, attention 2 / 2 / 2, clips_build 2 / 10 / 4, clips_build_f64 1 / 6 / 2, clips_repr
-1 / 9 / 3, color 1 / 8 / 4, ddpm 1 / 4 / 5, depth 1 / 7 / 2, export_smplx 1 / 3 / 3, export_smplx_blend 1 / 4 / 3, fit 1 / 7 / 14,
+1 / 9 / 3, color 1 / 8 / 4, ddpm 1 / 4 / 5, depth 1 / 7 / 2, export_smplx 1 / 3 / 3, export_smplx_blend 1 / 4 / 3, fit 1 / 7 / 14, fit_views 1 / 6 / 6,
 floor 1 / 8 / 19, gemm 1 / 2 / 7, gemm_res_layernorm 2 / 8 / 12, guidance_proj2d 1 / 2 / 5, guidance_skating 1 / 3 / 1,
-guidance_skating_split 1 / 3 / 1, keypoints 1 / 3 / 3, layernorm 1 / 1 / 2, metrics 1 / 11 / 8, optim 1 / 2 / 12, output_process
+guidance_skating_split 1 / 3 / 1, keypoints 1 / 3 / 3, layernorm 1 / 1 / 2, metrics 1 / 11 / 8, multiview 1 / 10 / 4, optim 1 / 2 / 12, output_process
 2 / 6 / 12, planes 2 / 16 / 19, posenet_forward 9 / 18 / 18, posenet_guided 1 / 6 / 3, posenet_loop 3 / 9 / 9, posenet_train
-4 / 24 / 100 (22 of every 25 are parameters), repr 1 / 11 / 5, repr_stats 1 / 6 / 2, smplx_forward 8 / 20 / 24, smplx_joints 1 / 2 / 4,
+4 / 24 / 100 (22 of every 25 are parameters), repr 1 / 11 / 5, repr_stats 1 / 6 / 2, rig 1 / 12 / 7, smplx_forward 8 / 20 / 24, smplx_joints 1 / 2 / 4,
 track_quality 1 / 5 / 7, track_resample 1 / 8 / 0, train_helpers 1 / 7 / 7, trajnet_forward 7 / 14 / 21, trajnet_loop 14 / 42 / 56,
-trajnet_train 3 / 12 / 738 (186 / 270 / 270 parameters).  Wall time of the whole module, 182 tests: 21 s as measured (the slowest
-test 1.4 s); every case runs four times (two plain runs, one guarded, one on canvases), the eleven of (d) a fifth time."""
+trajnet_train 3 / 12 / 738 (186 / 270 / 270 parameters).  In (d') 4 / 6 / 7 inputs and 10 / 6 / 12 allocations (multiview / fit_views
+/ rig) sit one element past a boundary; rohm_rig_pair_ws_bytes (4224) and rohm_rig_ba_ws_bytes (20000) are held to their number as
+well.  Wall time of the whole module, 182 tests: 21 s as measured run alone (the slowest test 1.4 s); with the three header cases,
+194 tests, 16.6 s summed over its tests when run after tests/test_gpu_stale_memory.py in one process (the slowest 0.72 s; each of
+the twelve tests of the three header cases below 5 ms).  Every case runs four times (two plain runs, one guarded, one on
+canvases), the eleven of (d) and the three of (d') a fifth time, those three a sixth time for the count of their calls."""
 import contextlib
 
 import numpy as np
@@ -77,6 +86,7 @@ import pytest
 import torch
 
 import guarded_memory as GM
+import header_cases as HC
 import stale_memory as SM
 import test_gpu_stale_memory as G
 from helpers import seeded
@@ -199,11 +209,6 @@ PARAMS_ON_CANVASES = {'posenet_train': 22, 'trajnet_train': 186}       # family 
 NO_INPUT_THROUGH_D = {'track_resample': 'every input is a numpy array the wrapper uploads itself'}
 
 
-def _snapshot(out):
-    torch.cuda.synchronize()
-    return [(label, t.detach().clone()) for label, t in out]
-
-
 _BASE, _ALIGNED = {}, {}
 
 
@@ -213,7 +218,7 @@ def _base(name):
         fn = ALL[name]
         base = G._run(fn, SM.ZEROS)
         assert base and all(t.numel() > 0 for _, t in base)
-        repeatable = not G._differences(G._run(fn, SM.ZEROS), base)
+        repeatable = not SM.differences(G._run(fn, SM.ZEROS), base)
         assert repeatable or name in G.ORACLE, f'{name}: two zero-filled runs differ and the case names no oracle'
         _BASE[name] = (base, repeatable)
     return _BASE[name]
@@ -222,7 +227,7 @@ def _base(name):
 def _hold_to_base(name, got, what):
     base, repeatable = _base(name)
     if repeatable:
-        diff = G._differences(got, base)
+        diff = SM.differences(got, base)
         assert not diff, f'{name}: {what} changes the result: {diff[:3]}'       # (output, (first differing element, value here, baseline))
     else:
         G.ORACLE[name](got)
@@ -269,7 +274,7 @@ def test_no_access_outside_outputs_workspaces_scratch_and_saved_buffers(name):
     fn = ALL[name]
     _base(name)
     with GM.guard() as g, _byte_counts() as calls:
-        got = _snapshot(fn())
+        got = SM.snapshot(fn())
         bad = g.violations()
     print(f'{name}: {g.served} guarded allocations, {sum(r.nbytes for r in g.records)} bytes, {g.unguarded} unguarded, '
           f'byte counts {sorted(set(calls))}')
@@ -328,8 +333,9 @@ def _is_clip_batch(t):
     return t.dtype == torch.float32 and t.dim() in (4, 5) and tuple(t.shape[-3:-1]) == (294, 1)
 
 
-def _placed_run(name, slices=False):
-    """Run the case with `_d` placing every input on a canvas ('slice' for the [.., 294, 1, T] float32 operands when `slices`) and,
+def _placed_run(name, slices=False, offset=False):
+    """Run the case with `_d` placing every input on a canvas ('slice' for the [.., 294, 1, T] float32 operands when `slices`, 'offset'
+    for every operand when `offset`) and,
     for the training families, every parameter on a canvas of its own -> (outputs, canvases, the in-place canvases' labels)."""
     fn, fam = ALL[name], G.family(name)
     canv = []
@@ -339,7 +345,7 @@ def _placed_run(name, slices=False):
         assert t.is_contiguous(), f'{name}: input {label} {tuple(t.shape)} is not contiguous and cannot be placed'
         if slices and _is_clip_batch(t):
             return GM.place(t.reshape(-1, 294, 1, t.shape[-1]), 'slice', device=DEV, into=canv, label=label).view(t.shape)
-        return GM.place(t, 'aligned', device=DEV, into=canv, label=label)
+        return GM.place(t, 'offset' if offset else 'aligned', device=DEV, into=canv, label=label)
 
     def with_parameters_on_canvases(make):
         def made(*a, **k):
@@ -360,7 +366,7 @@ def _placed_run(name, slices=False):
             m.setattr(G, '_make_trajnet', with_parameters_on_canvases(G._make_trajnet))
         with SM.poison(SM.ZEROS):
             raw = fn()
-            got = _snapshot(raw)
+            got = SM.snapshot(raw)
     at = {t.data_ptr() for label, t in raw if label in INPLACE.get(fam, ())}
     inplace = {c.label for c in canv if c.view.data_ptr() in at} | (INPLACE_CANVAS.get(fam, set()) & {c.label for c in canv})
     return got, canv, inplace
@@ -411,9 +417,48 @@ def test_batch_slices_give_the_bits_of_the_aligned_run(name):
     assert len(sliced) >= 2 and all(c.view.data_ptr() % 16 == 8 for c in sliced)
     if G.family(name) in PARAMS_ON_CANVASES:
         assert sum(c.label.startswith('parameter ') for c in canv) >= PARAMS_ON_CANVASES[G.family(name)]
-    diff = G._differences(got, want)
+    diff = SM.differences(got, want)
     assert not diff, f'{name}: a batch slice changes the result: {diff[:3]}'
     _hold_canvases(name, canv, inplace)
+
+
+OFFSET = sorted(HC.CASES)      # the headers that promise in so many words that an operand "needs the alignment of its element only"
+
+
+@pytest.mark.parametrize('name', OFFSET)
+def test_operands_one_element_past_a_boundary_give_the_bits_of_the_aligned_run(name):
+    """(d'): every input on an 'offset' canvas and every allocation of the wrappers from `guard(offset=True)` (which asserts the
+    address of each): inputs, outputs and workspaces all start one element past a 512-byte boundary."""
+    want = _aligned(name)[0]
+    with GM.guard(offset=True) as g:
+        got, canv, inplace = _placed_run(name, offset=True)
+        bad = g.violations()
+    print(f'{name}: {len(canv)} inputs and {g.served} allocations one element past a boundary')
+    assert canv and all(c.placement == 'offset' and c.view.data_ptr() % GM.ALIGN == c.view.element_size() for c in canv)
+    assert g.served > 0 and not g.passed_through, g.passed_through
+    assert not bad, f'{name}: bytes outside an allocation were written: {bad[:5]}'
+    diff = SM.differences(got, want)
+    assert not diff, f'{name}: operands one element past a boundary change the result: {diff[:3]}'
+    _hold_canvases(name, canv, inplace)
+
+
+@pytest.mark.parametrize('name', sorted(HC.CASES))
+def test_a_header_case_runs_every_declaration_of_its_header(name):
+    """Counted through the loaded library: the case calls every function its header declares -- the host-only ones (rohm_mv_limits,
+    the two `*_ws_bytes`) included, no exemptions -- and counting changes no result."""
+    from rohm_amd import _lib
+    declared = {f for f, _ in SM.declarations(SM.abi_headers()[HC.CASES[name][0]])}
+    assert declared and declared <= set(_lib.SIGNATURES)
+    handle, seen = _lib.lib(), set()
+    with pytest.MonkeyPatch.context() as m:
+        for fname in declared:
+            def counted(*a, _real=getattr(handle, fname), _name=fname):
+                seen.add(_name)
+                return _real(*a)
+            m.setattr(handle, fname, counted)
+        got = G._run(ALL[name], SM.ZEROS)
+    assert seen == declared, sorted(declared - seen)
+    _hold_to_base(name, got, 'counting the calls')
 
 
 # ================================================================================================ (e): the check can fail

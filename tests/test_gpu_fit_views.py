@@ -309,6 +309,22 @@ def test_outputs_do_not_depend_on_what_their_memory_held():
             assert SM.first_difference(a, b) is None, (name, label, SM.first_difference(a, b))
 
 
+def test_the_contract_case_matches_the_restatement():
+    """The inputs of `fit_views[...]` (tests/header_cases.py), which the four contract families only compare with themselves bit for
+    bit, held to the restatement: statuses, normal equations and start energy with bar (a), and the two conditions on E_end."""
+    import header_cases as HC
+    i = HC.fit_views_inputs(7)
+    out = dict(HC.fit_views_call(HC.tensors(HC.fit_views_inputs, 7, lambda t: t.to(DEV))))
+    ws, wst, sigma, conf_min, iters, min_obs = HC.FV_SCALARS[0]
+    pw, rw, sw, nw = VR.fit_views_pose(mdl(), i['kp'], i['cams'], i['betas'], i['init'], prev=i['prev'], w_prior=i['w_prior'], w_smooth=ws,
+                                       w_smooth_t=wst, sigma_px=sigma, conf_min=conf_min, iters=iters, min_obs=min_obs, want_normal=True)
+    r, n = out['report'].cpu().numpy(), out['normal'].cpu().numpy()
+    assert rw[:, 0].tolist() == [1, 0, 1] and np.array_equal(r[:, 0], rw[:, 0]) and np.array_equal(r[:, 6], rw[:, 6])
+    for f in (0, 2):
+        assert np.abs(n[f] - nw[f]).max() <= BAR * np.abs(nw[f]).max() and abs(r[f, 1] - rw[f, 1]) <= BAR * rw[f, 1]
+        assert r[f, 2] <= r[f, 1] and r[f, 2] <= 1.05 * rw[f, 2]
+
+
 # ---- bad arguments --------------------------------------------------------------------------------------------------------------------------
 def test_bad_arguments_are_refused_by_name():
     from rohm_amd import _lib

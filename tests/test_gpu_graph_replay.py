@@ -11,8 +11,9 @@ waits in Python right after its launch (it reads sums back, or uploads an index 
 rohm_amd._lib and the case says so: rohm_amass_preprocess, rohm_amass_metrics, rohm_scene_metrics, rohm_traj_report,
 rohm_track_quality.  What a wrapper allocates while recording comes from the graph's own pool and is filled with all-ones bytes by
 a RECORDED fill; buffers that exist before the capture (a handle's cached workspace, the case's own outputs and scratch) are
-poisoned between replays.  Together graph_replay.REPLAYED (68 entry points, 26 cases) and REFUSED_WHILE_RECORDING (3) are the
-header's 71 stream-taking functions; EXEMPT is empty, and the call logs hold REPLAYED to the truth family by family.
+poisoned between replays.  Together graph_replay.REPLAYED (75 entry points, 29 cases) and REFUSED_WHILE_RECORDING (3) are the
+public headers' 78 stream-taking functions; EXEMPT is empty, and the call logs hold REPLAYED to the truth family by family.
+The cases of rohm_multiview.h, rohm_fit_views.h and rohm_rig.h are those of tests/header_cases.py, value sets 7 and 8 in the slots.
 Several families of stale_memory.COVERAGE share one case on purpose where their entry points feed one another or share their
 inputs (ops: GEMM, LayerNorm GEMM, output head, attention; render: depth -> probe -> mask, normals -> colour; data: the ten
 data-side calls of one recording; metrics; track): one graph of 7 - 35 nodes instead of ten, and the entry points are recorded in
@@ -63,13 +64,14 @@ What stays unseen -- nobody should take it for covered:
   * the clip-resident TrajNet loop: it waits, so under a capture it steps aside (asserted: rohm_trajnet_loop_mode() == 0 for the
     recording call) and the launch-per-layer form is what replays.
 
-Numbers (MI355X, the default environment: four hardware queues, nothing set).  26 cases, 26 graphs of the cases plus 10 small ones
-(the three planted checks, three refusals, the pageable copy, three Python-layer refusals), 108 replays by the cases, 10756 nodes in
-the cases' graphs (hipGraphGetNodes on the kept graph).  The 130-step TrajNet graph: 7704 nodes in one chain (no fork), capture
+Numbers (MI355X, the default environment: four hardware queues, nothing set).  29 cases, 29 graphs of the cases plus 10 small ones
+(the three planted checks, three refusals, the pageable copy, three Python-layer refusals), 117 replays by the cases, 10797 nodes in
+the cases' graphs (hipGraphGetNodes on the kept graph; the three header cases: 13 / 8 / 20 nodes, 5 - 9 ms each).  The 130-step TrajNet graph: 7704 nodes in one chain (no fork), capture
 0.009 s, instantiation 0.007 s (timed by itself, `CUDAGraph.instantiate()`); the other graphs 1 - 781 nodes, capture 0.001 - 0.021 s,
 instantiation at most 0.006 s (the forked TrajControl graph) -- so the long graph is not slow to instantiate; its whole case takes
 0.44 s.  Slowest case: train[TrajControl, B2, T16], 781 nodes, 0.9 - 1.1 s in run_case (1.7 s as a test, with the module's set-up);
-all cases 3.4 s.  Wall time of the whole module, 36 tests, run alone: 11.1 s."""
+all cases 3.4 s.  Wall time of the whole module, 36 tests, run alone: 11.1 s; with the three header cases, 39 tests, after the other
+three families in one process: all cases 2.5 s, 6.6 s summed over its tests."""
 import ctypes as C
 
 import numpy as np
@@ -77,7 +79,9 @@ import pytest
 import torch
 
 import graph_replay as GR
+import header_cases as HC
 import stale_memory as SM
+import stream_order as SO
 import test_gpu_stale_memory as G
 from helpers import seeded
 
@@ -1033,6 +1037,23 @@ def _track():
                                'rohm_fit_shape_moments'])
 
 
+# ---- the headers next to rohm_hip.h ----------------------------------------------------------------------------------------------------
+def _header_case(header, inputs, call):
+    """The case of tests/header_cases.py: value sets 7 and 8 in the slots; every stream-taking function of the header, and nothing
+    else, is recorded."""
+    s = GR.Slots(DEV)
+    for k in inputs(7):
+        s.add(k, torch.from_numpy(np.array(inputs(7)[k])), torch.from_numpy(np.array(inputs(8)[k])))
+    claims = set(SO.abi_stream_functions(SM.abi_headers()[header]))
+    r = GR.run_case(s, lambda s, h: call({k: s[k] for k in inputs(7)}), dict, _nothing, _side(), claims=claims)
+    assert r['replays'] >= 3 and r['log'].recorded() == claims
+    return r
+
+
+for _name, _case in HC.CASES.items():
+    case(_name)(lambda c=_case: _header_case(*c))
+
+
 # ================================================================================================ the tests
 @pytest.mark.parametrize('name', sorted(CASES))
 def test_a_replay_does_what_the_recorded_call_would_do_again(name):
@@ -1051,7 +1072,7 @@ def test_the_control_stream_and_the_one_stream_order_replay_the_same_bits():
     for r in (a, b):
         if isinstance(r, BaseException):
             raise r
-    assert a['final'] and not GR.differences(a['final'], b['final'])
+    assert a['final'] and not SM.differences(a['final'], b['final'])
     # ... and they are two DIFFERENT graphs: the one-stream capture is a chain; with the control stream the graph forks (the caller's
     # stream hands the time table, and from step 2 on the "consumed" events, to the branch) and holds more edges than a chain
     (na, ea, fa), (nb, eb, fb) = a['shape'], b['shape']

@@ -115,6 +115,20 @@ def test_options_move_kernel_and_restatement_alike(_margins):
         assert (np.abs(report[has][:, 1:3] - ref['report'][has][:, 1:3]) / ref['report'][has][:, 1:3]).max() <= BAR
 
 
+def test_the_contract_case_matches_the_restatement():
+    """The inputs of `multiview[...]` (tests/header_cases.py), which the four contract families only compare with themselves bit for
+    bit, held to the restatement with this module's bars."""
+    import header_cases as HC
+    i = HC.multiview_inputs(7)
+    out = dict(HC.multiview_call(HC.tensors(HC.multiview_inputs, 7, lambda t: t.to(DEV))))
+    ref = MR.triangulate(i['kp'], i['cams'], rigid=i['rigid'])
+    assert len(MR.margins_ok(ref)) == 0
+    assert np.array_equal(out['inliers'].cpu().numpy().astype(np.int64), ref['inliers'].astype(np.int64))
+    has = ref['report'][..., 0] > 0
+    d = np.abs(out['joints'].cpu().numpy()[has] - ref['joints'][has]).max(-1) / np.maximum(1.0, np.linalg.norm(ref['joints'][has], axis=-1))
+    assert has.any() and (~has).any() and d.max() <= BAR
+
+
 def test_the_same_bits_twice():
     case = MR.build_case('many_points')
     a, b = run(case), run(case)

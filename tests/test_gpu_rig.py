@@ -178,6 +178,44 @@ def test_the_same_bits_twice_and_over_poisoned_memory():
             assert np.array_equal(a, b), (k, pattern)
 
 
+def test_the_contract_case_matches_the_restatement():
+    """The inputs of `rig[...]` (tests/header_cases.py), which the four contract families only compare with themselves bit for bit,
+    held to the restatement with this module's bars and margins."""
+    import header_cases as HC
+    i = HC.rig_inputs(7)
+    out = {k: v.cpu().numpy() for k, v in HC.rig_call(HC.tensors(HC.rig_inputs, 7, lambda t: t.to(DEV)))}
+    ref = RR.pair_hypotheses(i['kp'], i['cams'], i['pairs'], i['samples'])
+    live = ref['counts'][..., 0] >= 0
+    assert live.any() and (~live).any() and (ref['margin_tau'][live] >= 1e-6).all()
+    assert np.array_equal(out['counts'], ref['counts']) and np.array_equal(out['best'], ref['best'])
+    ok = RR.margins_ok(ref)
+    assert ok.sum() >= 0.95 * live.sum() and np.abs(out['E_all'][ok] - ref['E'][ok]).max() <= BAR
+    m = RR.ba_moments(i['kp'], i['cams'], i['points'])
+    assert np.abs(out['S'] - m['S']).max() <= BAR * np.abs(m['S']).max() and out['stats'][1] == m['n_obs']
+
+
+def test_ba_update_without_cams_new_computes_no_cameras_and_keeps_the_points():
+    """`cams_new` NULL is not computed, and nothing else changes: `points_new`, one element past a 512-byte boundary between guard
+    bands, keeps every bit of the call that had `cams_new`."""
+    import guarded_memory as GM
+    import header_cases as HC
+    from rohm_amd import _lib, rig
+    from rohm_amd._lib import check, ptr, stream_ptr
+    t = HC.tensors(HC.rig_inputs, 7, lambda t: t.to(DEV))
+    canv = []
+    Xn = GM.place(torch.zeros(HC.RIG_P, 3, dtype=torch.float64), 'offset', device=DEV, into=canv)
+    cn = torch.empty(HC.RIG_V, 24, dtype=torch.float64, device=DEV)
+    for cams_new in (cn, None):
+        check(_lib.lib().rohm_rig_ba_update(ptr(t['kp']), ptr(t['cams']), ptr(t['points']), ptr(t['dc']), HC.RIG_V, HC.RIG_N, HC.RIG_J, 0.2, 10.0,
+                                            1e-3, ptr(Xn), ptr(cams_new), stream_ptr(torch.device(DEV))), 'rohm_rig_ba_update')
+        torch.cuda.synchronize()
+        if cams_new is not None:
+            want = rig.ba_update(t['kp'], t['cams'], t['points'], t['dc'])
+            assert SM.first_difference(Xn, want[0]) is None and SM.first_difference(cn, want[1]) is None
+            before = canv[0].flat.clone()
+    assert torch.equal(canv[0].flat, before)
+
+
 def test_wrappers_refuse_bad_arguments():
     from rohm_amd import rig
     from rohm_amd._lib import RohmHipError

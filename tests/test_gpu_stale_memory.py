@@ -42,6 +42,7 @@ import numpy as np
 import pytest
 import torch
 
+import header_cases as HC
 import stale_memory as SM
 from helpers import PoseDataset, seeded
 from rohm_amd.utils import synth
@@ -708,17 +709,17 @@ def _optim():
     return out
 
 
+# ================================================================================================ the headers next to rohm_hip.h
+for _name, (_, _inputs, _call) in HC.CASES.items():         # rohm_multiview.h, rohm_fit_views.h, rohm_rig.h: every declaration of each
+    case(_name)(lambda i=_inputs, c=_call: c(HC.tensors(i, 7, lambda t: _d(t))))     # (`_d` as it is at the call: other modules replace it)
+
+
 # ================================================================================================ the tests
 def _run(fn, word):
     with SM.poison(word):
         out = fn()
         torch.cuda.synchronize()
-    return [(label, t.detach().clone()) for label, t in out]
-
-
-def _differences(got, want):
-    assert [l for l, _ in got] == [l for l, _ in want]
-    return [(label, d) for (label, a), (_, b) in zip(got, want) for d in [SM.first_difference(a, b)] if d is not None]
+    return SM.snapshot(out)
 
 
 @pytest.mark.parametrize('name', sorted(CASES))
@@ -728,13 +729,13 @@ def test_outputs_do_not_depend_on_what_uninitialised_memory_held(name):
     fn = CASES[name]
     base = _run(fn, SM.ZEROS)
     assert base and all(t.numel() > 0 for _, t in base)
-    repeatable = not _differences(_run(fn, SM.ZEROS), base)
+    repeatable = not SM.differences(_run(fn, SM.ZEROS), base)
     assert repeatable or name in ORACLE, f'{name}: two zero-filled runs differ and the case names no oracle'
     failures = {}
     for pname, word in SM.PATTERNS.items():
         got = _run(fn, word)
         if repeatable:
-            diff = _differences(got, base)
+            diff = SM.differences(got, base)
             if diff:
                 failures[pname] = diff[:3]          # (output, (first differing element, poisoned value there, baseline value))
         else:
@@ -753,8 +754,8 @@ def test_no_state_is_carried_from_one_call_to_the_next(name):
         got = [(l, t.clone()) for l, t in call(h, 1)]
         again = [(l, t.clone()) for l, t in call(h, 0)]
         torch.cuda.synchronize()
-    assert not _differences(got, want), (name, _differences(got, want)[:3])
-    assert not _differences(again, first), (name, _differences(again, first)[:3])
+    assert not SM.differences(got, want), (name, SM.differences(got, want)[:3])
+    assert not SM.differences(again, first), (name, SM.differences(again, first)[:3])
 
 
 # ---- one address, a sequence of shapes ------------------------------------------------------------------------------------------
@@ -801,7 +802,7 @@ def _sequence(rec, steps, refs):
         rec.begin()
         got = [(l, t.clone()) for l, t in thunk()]
         torch.cuda.synchronize()
-        diff = _differences(got, refs[key])
+        diff = SM.differences(got, refs[key])
         assert not diff, f'call {n} ({key}) in recycled memory differs from the call in fresh zero-filled memory: {diff[:3]}'
 
 
@@ -871,6 +872,6 @@ def test_posenet_module_alternating_batch_sizes(chain):
     first = _pose_forward(net, 3, 143)
     one = _pose_forward(net, 1, 143)
     for _ in range(39):
-        assert not _differences(_pose_forward(net, 1, 143), one)
-    assert not _differences(_pose_forward(net, 3, 143), first)
-    assert not _differences(_pose_loop(net, 3, 143), _pose_loop(_make_posenet(chain), 3, 143))
+        assert not SM.differences(_pose_forward(net, 1, 143), one)
+    assert not SM.differences(_pose_forward(net, 3, 143), first)
+    assert not SM.differences(_pose_loop(net, 3, 143), _pose_loop(_make_posenet(chain), 3, 143))

@@ -6,7 +6,7 @@ tests/test_gpu_stale_memory.py poisons what a buffer holds and tests/test_gpu_bo
 torch's default stream with their inputs long finished.  There a kernel, memset or copy that the library issues on stream 0 or on a
 stream of its own without an event, or a wrapper that passes the wrong stream, is invisible: the stray work finds its inputs ready
 and its consumer waits long enough anyway.  A hidden wait changes no result at all.  Here every case of that registry (imported, not
-copied: `G.CASES`, `G._run`, `G._differences`, and `EXTRA` of tests/test_gpu_bounds.py) runs once more
+copied: `G.CASES`, `G._run`, `stale_memory.differences`, and `EXTRA` of tests/test_gpu_bounds.py) runs once more
 
   (1) plainly on the default stream: the baseline (`test_gpu_bounds._base`: two runs, so first-call probes are out of the way and
       repeatability is established; rule (b) of the stale-memory module applies unchanged, no case needs it), and a third plain run
@@ -39,7 +39,7 @@ stream showed both.  The same was checked once against the library itself, in an
 stream 0 and rohm_layernorm_f32 synchronising its stream: the ddpm case failed on (3)
 (`ddpm_step`, element 0 NaN), the layernorm case on (4) (rohm_layernorm_f32, 25.0 ms: the whole gate), their neighbours passed.
 
-Coverage: every header function with a `rohm_stream_t` parameter (71) returned at least once with the gate closed (68, among them
+Coverage: every function of the public headers with a `rohm_stream_t` parameter (78) returned at least once with the gate closed (75, among them
 rohm_trajnet_sample_loop in its `resident 0` cases) or is documented as waiting (rohm_posenet_exchange_status, rohm_track_resample,
 rohm_floor_hypotheses); STREAM_EXEMPT is empty.  The call log also holds stale_memory.COVERAGE and test_gpu_bounds.EXTRA_COVERAGE to
 the truth: every family's cases really call what the tables claim (they did: no table needed a correction).
@@ -78,9 +78,11 @@ Numbers (MI355X).  Gate length: the slowest host side of a single entry point in
 every other entry point stays below 0.025 ms.  4 x 1.54 ms = 6.2 ms is below the floor, so `min_remaining` is 10 ms for every case
 (each case takes max(10 ms, 4 x its own slowest plain call)) and a gate is twice that, 20 ms, sized with a quarter more delay
 cycles than calibrated (2.39e6 per ms).  A gate that is too short fails check (4); it cannot pass silently.
-Sizes: 83 cases (78 of the registry, 5 of EXTRA), 181 logged calls and 304 gates in the gated runs, at most 11 gates per case (repr);
-the gated runs take 8.7 s in all, 0.025 - 0.30 s each.  Wall time of the whole module, 87 tests, run alone: 27 s as measured, next
-to the 21 s of tests/test_gpu_bounds.py (the slowest test 1.5 s); after that module in one process the baselines are shared."""
+Sizes: 86 cases (81 of the registry, 5 of EXTRA), 190 logged calls and 318 gates in the gated runs, at most 11 gates per case;
+the gated runs take 9.7 s in all, 0.025 - 0.41 s each (the three header cases: 3 / 2 / 4 calls, asserted from LOGGED_CALLS, one gate
+and 0.026 s each).  Wall time of the whole module, 87 tests, run alone: 27 s as measured, next to the 21 s of
+tests/test_gpu_bounds.py (the slowest test 1.5 s); after that module in one process the baselines are shared: 90 tests, 14.1 s
+summed over its tests (the slowest 0.69 s)."""
 import contextlib
 import time
 
@@ -100,6 +102,10 @@ STREAM_AT = SO.abi_stream_functions()           # entry point -> position of its
 MIN_REMAINING = 0.010                           # seconds of gate a call must find left, at least (Numbers in the docstring)
 MARGIN = 4                                      # ... and this many times the slowest call of the case's plain run
 MAX_SIDE_STREAMS = 8
+# the gated run of these cases logs exactly this many calls: two triangulations and the residuals; the fit with and without its
+# optional operands; the four stream-taking functions of rohm_rig.h
+LOGGED_CALLS = {'multiview[V4, N3, J22]': 3, 'fit_views[V3, N3, dead middle frame]': 2, 'rig[V4, N3, J22, Q6, K5]': 4}
+assert set(LOGGED_CALLS) <= set(ALL)
 
 
 # ================================================================================================ one measured run
@@ -198,7 +204,7 @@ def _harness():
             for kind, wrong in strays.items():
                 r = _measure('planted stray: ' + kind, _chain, 'planted', side, delay, rate, gated_fn=lambda w=wrong: _chain(w))
                 assert r['error'] is None, r['error']
-                seen[kind] = bool(G._differences(r['got'], r['plain']))
+                seen[kind] = bool(SM.differences(r['got'], r['plain']))
             tried.append(seen)
             if all(seen.values()):
                 _HARNESS.update(side=side, attempt=attempt, rate=rate)
@@ -215,7 +221,7 @@ def test_both_planted_strays_are_reported_and_pick_the_side_stream():
     print(f'side stream: attempt {h["attempt"]} of {MAX_SIDE_STREAMS}, {h["rate"]:.0f} delay units per ms, tried {h["tried"]}')
     assert all(h['tried'][-1].values()) and h['attempt'] == len(h['tried'])
     r = _measure('planted: no stray', _chain, 'planted', h['side'], h['delay'], h['rate'])      # ... and the chain in stream order passes
-    assert r['error'] is None and not G._differences(r['got'], r['plain']) and r['inputs'].complete() and r['gates'] >= 1
+    assert r['error'] is None and not SM.differences(r['got'], r['plain']) and r['inputs'].complete() and r['gates'] >= 1
 
 
 class _StandIn:
@@ -243,7 +249,7 @@ def test_a_planted_wait_is_reported():
         return [('x', x)]
     r = _measure('planted wait', fn, 'planted', h['side'], h['delay'], h['rate'], lib_obj=fake,
                  stream_at={'rohm_fake_launch': 1, 'rohm_fake_wait': 1})
-    assert r['error'] is None and not G._differences(r['got'], r['plain'])
+    assert r['error'] is None and not SM.differences(r['got'], r['plain'])
     assert [(f, closed) for f, _, closed in r['log'].calls] == [('rohm_fake_launch', True), ('rohm_fake_wait', False), ('rohm_fake_launch', True)]
     unproven = r['log'].unproven()
     assert [f for f, _ in unproven] == ['rohm_fake_wait'] and unproven[0][1] > 0.0
@@ -272,11 +278,11 @@ def _result(name):
         out = dict(error=r['error'], diff=None, oracle_error=None, repeatable=repeatable, gates=r['gates'], seconds=r['seconds'],
                    min_remaining=r['min_remaining'], slowest=r['slowest'], calls=r['log'].functions() | r['plain_log'].functions(),
                    proven=r['log'].proven(), unproven=r['log'].unproven(lambda f: SO.may_wait(f, name)),
-                   n_calls=len(r['log'].calls), plain_diff=G._differences(r['plain'], base) if repeatable else [],
+                   n_calls=len(r['log'].calls), plain_diff=SM.differences(r['plain'], base) if repeatable else [],
                    inputs=(r['inputs'].replayed, len(r['inputs'].staged)))
         if r['error'] is None:
             if repeatable:
-                out['diff'] = G._differences(r['got'], base)
+                out['diff'] = SM.differences(r['got'], base)
             else:
                 try:
                     G.ORACLE[name](r['got'])
@@ -303,6 +309,7 @@ def test_calls_work_on_the_callers_stream_and_do_not_wait(name):
     assert not r['unproven'], (f'{name}: calls returned with the gate open (they waited for the stream, or took longer than '
                                f'{1e3 * r["min_remaining"]:.1f} ms): {[(f, f"{1e3 * s:.3f} ms") for f, s in r["unproven"]]}')
     assert r['n_calls'] > 0 and r['gates'] <= 64, (r['n_calls'], r['gates'])
+    assert r['n_calls'] == LOGGED_CALLS.get(name, r['n_calls']), r['n_calls']
 
 
 def test_every_stream_taking_entry_point_is_proven_documented_or_exempt_and_the_coverage_tables_are_true():

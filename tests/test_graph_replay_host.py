@@ -39,7 +39,7 @@ def test_every_refusal_is_a_sentence_of_the_header():
 def test_every_exemption_has_a_reason_and_every_replayed_entry_a_family():
     assert all(isinstance(r, str) and len(r) > 20 for r in GR.EXEMPT.values())      # (EXEMPT is empty today)
     assert set(GR.REPLAYED.values()) == {'ops', 'planes', 'ddpm', 'posenet', 'trajnet', 'train', 'guided', 'smplx', 'repr', 'export', 'render', 'image',
-                                          'train_helpers', 'data', 'metrics', 'track'}
+                                          'train_helpers', 'data', 'metrics', 'track', 'multiview', 'fit_views', 'rig'}
 
 
 @pytest.mark.parametrize('a, lo, hi', [

@@ -1,6 +1,6 @@
 """Host side of the guarded-memory tests (tests/test_gpu_bounds.py), on CPU tensors: the guarded allocators return what was asked for
 inside intact bands and go away again, a store one element outside a view is reported with its offset, a load there is NaN, inputs
-placed on a canvas round-trip and a change of one bit is noticed; and every entry point of include/rohm_hip.h that can be handed a
+placed on a canvas round-trip and a change of one bit is noticed; and every entry point of the public headers that can be handed a
 caller's tensor is run by a guarded-memory case or exempt by name."""
 import pytest
 import torch
@@ -145,6 +145,28 @@ def test_slice_placement_is_a_batch_slice_eight_bytes_past_a_sixteen_byte_bounda
         GM.place(torch.zeros(4, 6).t(), 'aligned')
 
 
+@pytest.mark.parametrize('dtype', DTYPES, ids=lambda d: str(d).replace('torch.', ''))
+def test_offset_placement_and_the_offset_guard_start_one_element_past_a_boundary(dtype):
+    size = torch.empty((), dtype=dtype).element_size()
+    src, canv = torch.arange(35).reshape(5, 7).to(dtype), []
+    t = GM.place(src, 'offset', into=canv, label='src')
+    c = canv[0]
+    assert torch.equal(t, src) and t.is_contiguous() and t.data_ptr() % GM.ALIGN == size and '(offset)' in c.describe()
+    assert c.untouched() and c.offset >= GM.BAND + size and c.flat.numel() - c.offset - c.nbytes >= GM.BAND
+    _outside(t, -1).fill_(0)                                                      # the element between the boundary and the operand is band
+    assert not c.bands_untouched() and c.first_change() == -size
+    with GM.guard(CPU, offset=True) as g:
+        a, z = torch.empty(5, 3, dtype=dtype), torch.ones(2, dtype=dtype).new_zeros((4,))
+        assert a.data_ptr() % GM.ALIGN == size and z.data_ptr() % GM.ALIGN == size and not a.any() and not z.any()
+        a.fill_(1)
+        assert g.violations() == [] and g.served == 2 and g.unguarded == 0
+        _outside(a, -1).fill_(0)
+        _outside(z, 4).fill_(0)
+        assert [(i, off) for i, _, off in g.violations()] == [(0, -size), (1, 4 * size)]
+    with GM.guard(CPU) as g:                                                      # and without the option allocations are aligned as before
+        assert torch.empty(3, dtype=dtype).data_ptr() % GM.ALIGN == 0
+
+
 def test_another_band_word_is_kept_around_the_operand():
     canv = []
     t = GM.place(torch.ones(6), 'aligned', into=canv, band=b'\x01\x00\xc0\x7f')
@@ -160,7 +182,7 @@ def test_the_header_parser_finds_the_pointer_taking_entry_points():
               '/* int rohm_d(float* x); */\nsize_t rohm_e(int M, int N);\nvoid rohm_f(rohm_smplx_t* h);\n')
     assert SM.abi_pointer_functions(sample) == {'rohm_a': ['x', 'out'], 'rohm_c': ['params', 'grads', 'numel', 'gap', 'idx', 'bits', 'ws']}
     fns = SM.abi_pointer_functions()
-    assert len(fns) >= 76, sorted(fns)                                            # (as of this test; the guard test below names what is new)
+    assert len(fns) >= 84, sorted(fns)                                            # (as of this test; the guard test below names what is new)
     assert set(SM.abi_buffer_functions()) <= set(fns)
     assert fns['rohm_ddpm_step'] == ['x_t', 'x0', 'noise', 'guid_grad', 'x_prev']
     assert fns['rohm_floor_moments'] == ['points', 'plane', 'origin', 'out']

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import stale_memory as SM
+import stream_order as SO
 from helpers import PoseDataset
 from oracle import diffusion as odiff
 from rohm_amd import _lib
@@ -94,17 +96,34 @@ def test_no_cpu_fallback():
         net(batch, torch.zeros(1, dtype=torch.int64))
 
 
-def test_abi_exports_every_declared_symbol():
-    """librohm_hip.so loads and exports exactly what include/rohm_hip.h declares (no compute calls)."""
-    hdr = open(os.path.join(ROOT, 'include', 'rohm_hip.h')).read()
-    declared = set(re.findall(r'\b(rohm_[a-z0-9_]+)\s*\(', hdr))
-    assert declared, 'no declarations parsed'
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared:
-        assert hasattr(lib, name), f'{name} declared in rohm_hip.h but not exported'
-    assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
-    lib.rohm_version.restype = ctypes.c_int
-    assert lib.rohm_version() >= 100
+def test_abi_headers_table_and_library_agree():
+    """The headers of include/, `_lib.HEADERS`, `_lib.SIGNATURES` and the built library agree, for all headers together: the same
+    files, the same names, each declared once, every symbol exported with the row's types and as many ctypes arguments as the
+    declaration has parameters (no compute calls)."""
+    assert sorted(_lib.HEADERS) == sorted(f for f in os.listdir(os.path.join(ROOT, 'include')) if f.endswith('.h'))
+    headers = SM.abi_headers()
+    assert list(headers) == list(_lib.HEADERS) and _lib.HEADERS[0] == 'rohm_hip.h'
+    declared = {h: dict(SM.declarations(text)) for h, text in headers.items()}
+    names = [n for h in headers for n, _ in SM.declarations(headers[h])]
+    assert len(names) == len(set(names)), sorted(n for n in set(names) if names.count(n) > 1)      # no name in two headers, or twice in one
+    assert set(names) == set(_lib.SIGNATURES), set(names) ^ set(_lib.SIGNATURES)
+    assert len(names) >= 124
+    assert set(declared['rohm_multiview.h']) == {'rohm_mv_limits', 'rohm_mv_triangulate', 'rohm_mv_residuals'}
+    assert set(declared['rohm_fit_views.h']) == {'rohm_fit_views_pose'}
+    assert set(declared['rohm_rig.h']) == {'rohm_rig_pair_ws_bytes', 'rohm_rig_ba_ws_bytes', 'rohm_rig_pair_hypotheses', 'rohm_rig_pair_moments',
+                                           'rohm_rig_ba_moments', 'rohm_rig_ba_update'}
+    raw, L = ctypes.CDLL(_lib.LIB_PATH), _lib.lib()
+    for h in headers:
+        for name, params in declared[h].items():
+            assert hasattr(raw, name), f'{name} declared in {h} but not exported'
+            res, args = _lib.SIGNATURES[name]
+            fn = getattr(L, name)
+            assert fn.restype is res and list(fn.argtypes) == list(args), name
+            assert len(args) == len(params), f'{name}: {len(params)} parameters in {h}, {len(args)} ctypes arguments'
+    assert L.rohm_version() >= 100
+    for h in _lib.HEADERS[1:]:                  # the other headers include the first and take over its conventions by sentence
+        assert '#include "rohm_hip.h"' in headers[h], h
+        assert 'obey rohm_hip.h\'s "Conventions" and "Caller-owned memory" word for word' in SO.header_prose(headers[h]), h
 
 
 def _stream_k_walk(B, T=143, D=512, c_out=272):

@@ -331,21 +331,3 @@ def test_argument_errors_name_the_argument():
         assert word in L.rohm_last_error().decode()
     # N == 0 returns without a launch, whatever the pointers
     assert tri(N=0, kp=None, cams=None, joints=None, conf=None, report=None, inl=None) == 0 and res(N=0, jw=None, kp=None, cams=None, out=None) == 0
-
-
-def test_abi_table_matches_the_header():
-    """include/rohm_multiview.h against `_lib.SIGNATURES_MULTIVIEW` and the built library, as tests/test_host_logic.py holds
-    rohm_hip.h against `SIGNATURES`: the same declared set, every symbol exported, as many ctypes arguments as parameters."""
-    import os
-    import re
-    from rohm_amd import _lib
-    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'rohm_multiview.h')) as f:
-        text = re.sub(r'/\*.*?\*/', ' ', f.read(), flags=re.S)
-    declared = {m.group(1): [p for p in m.group(2).split(',') if p.strip() and p.strip() != 'void'] for m in re.finditer(r'\b(rohm_\w+)\s*\(([^;{}()]*)\)\s*;', text)}
-    assert set(declared) == set(_lib.SIGNATURES_MULTIVIEW) == {'rohm_mv_limits', 'rohm_mv_triangulate', 'rohm_mv_residuals'}
-    assert not set(_lib.SIGNATURES_MULTIVIEW) & set(_lib.SIGNATURES)
-    L = _lib.lib()
-    for name, (res, args) in _lib.SIGNATURES_MULTIVIEW.items():
-        fn = getattr(L, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args) and len(args) == len(declared[name]), name
-    assert '#include "rohm_hip.h"' in text

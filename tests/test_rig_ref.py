@@ -9,8 +9,6 @@ pair -- were run once with the restatement; the worst rotation / camera-centre e
 up: the factor of two is for seed-to-seed spread.  The median residual after bundle adjustment must be within 1.25 x the noise (at
 the optimum it is below the noise; 25 % covers the robust kernel's bias), and bundle adjustment must lower both errors."""
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
@@ -380,21 +378,6 @@ def test_argument_errors_name_the_argument():
     # Q == 0 returns without a launch, whatever the pointers
     assert hyp(Q=0, kp=None, cams=None, pairs=None, samples=None, ws=None, E=None, counts=None, best=None) == 0
     assert mom(Q=0, kp=None, cams=None, pairs=None, E=None, ws=None, out=None) == 0
-
-
-def test_abi_table_matches_the_header():
-    from rohm_amd import _lib
-    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'rohm_rig.h')) as f:
-        text = re.sub(r'/\*.*?\*/', ' ', f.read(), flags=re.S)
-    declared = {m.group(1): [p for p in m.group(2).split(',') if p.strip() and p.strip() != 'void'] for m in re.finditer(r'\b(rohm_\w+)\s*\(([^;{}()]*)\)\s*;', text)}
-    assert set(declared) == set(_lib.SIGNATURES_RIG) == {'rohm_rig_pair_ws_bytes', 'rohm_rig_ba_ws_bytes', 'rohm_rig_pair_hypotheses',
-                                                         'rohm_rig_pair_moments', 'rohm_rig_ba_moments', 'rohm_rig_ba_update'}
-    assert not set(_lib.SIGNATURES_RIG) & (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_MULTIVIEW) | set(_lib.SIGNATURES_FIT_VIEWS))
-    L = _lib.lib()
-    for name, (res, args) in _lib.SIGNATURES_RIG.items():
-        fn = getattr(L, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args) and len(args) == len(declared[name]), name
-    assert '#include "rohm_hip.h"' in text
 
 
 # ---- 9: the margins of the GPU inputs -------------------------------------------------------------------------------------------------------

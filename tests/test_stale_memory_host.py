@@ -1,6 +1,6 @@
 """Host side of the stale-memory tests (tests/test_gpu_stale_memory.py): the poisoning replacement of torch's uninitialised
-allocators really poisons and really goes away, and every entry point of include/rohm_hip.h that is handed a caller-owned
-buffer is run by a case of that module."""
+allocators really poisons and really goes away, and every entry point of the public headers (rohm_amd._lib.HEADERS) that is
+handed a caller-owned buffer is run by a case of that module."""
 import numpy as np
 import pytest
 import torch
