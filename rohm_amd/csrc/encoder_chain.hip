@@ -14,24 +14,21 @@
 // exchange through the L2 of the XCD they share (the block -> tile map of EPI_BIAS_RES_LN: partners dispatched back to back onto one
 // XCD), while the next phase's WEIGHT chunks, which depend on nobody, are already on their way into LDS underneath the epilogue.
 //
-// Arithmetic: every tile is computed exactly as gemm_f32_kernel<BN, EPI, 0, true> computes it (same fragments, same k order, same
-// LayerNorm statistics tree) -- the chain and the launch-per-GEMM path agree to the last bit or two (fma contraction of the epilogue
+// Arithmetic: the tile core is gemm_f32_kernel<BN, EPI, 0, true>'s (gemm_tile.h: same fragments, same k order, same LayerNorm
+// statistics tree) -- the chain and the launch-per-GEMM path agree to the last bit or two (fma contraction of the epilogue
 // expressions is the compiler's choice per instantiation; tests/test_gpu_chain.py).
-// Exchange discipline: gemm_f32.hip's -- tags from (salt + index) + 64 x the workspace's pass counter, bounded waits that report
+// Exchange discipline: tags from (salt + index) + 64 x the workspace's pass counter, bounded waits that report
 // into the error word, layout guard at create, fallback + re-run by the host (exchange.hip).
 #include <type_traits>
 #include "common.h"
-#include "gemm_sched.h"
+#include "gemm_tile.h"
 #include "attention_tile.h"
 
 namespace rohm {
 
-typedef float f32x16c __attribute__((ext_vector_type(16)));
-
 namespace chain {
 
-constexpr int BM = 144, BK = kGemmBK, NRB = BM / 16;
-constexpr int A_UNITS = BM * 8, A_ITERS = (A_UNITS + 255) / 256;      // 16-byte units per A chunk; the fifth pass is half populated
+using namespace gemm_tile;
 constexpr int kMaxBN = 384;
 // LDS: [A: 2 x 144 x 32] [W: 2 x BN x 32, BN <= 384] and, at a FIXED place behind the widest W buffers, the DMA landing zone and
 // the statistics / bias-row zone -- so that the next phase's weight chunks can land while this phase's epilogue still uses its zone
@@ -93,19 +90,11 @@ __device__ __forceinline__ void group_sync(unsigned long long* flags, int tn, in
         asm volatile("" ::: "memory");
     }
     if (tid < G && tid != tn) {
-        for (int it = 0;; ++it) {
-            const unsigned long long f = __hip_atomic_load(flags + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((unsigned)f == tag && (f >> 32) != 0ull) {
-                if ((unsigned)(f >> 32) != xcc1) __hip_atomic_store(err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-            if ((it & 127) == 127 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-            if (it > (1 << 19)) {
-                __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
+        wait_word(flags + tid, [&](unsigned long long f) __attribute__((always_inline)) {
+            if (!((unsigned)f == tag && (f >> 32) != 0ull)) return false;
+            if ((unsigned)(f >> 32) != xcc1) __hip_atomic_store(err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return true;
+        }, err, 1u);
     }
     __syncthreads();
     // No acquire fence here: at agent scope it is `buffer_inv sc1`, which on this multi-XCD part also drops the L2's lines of ordinary
@@ -158,6 +147,8 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
     const int m0 = p.m0, n0 = p.n0;
 
     // ---- staging -----------------------------------------------------------------------------------------------------------
+    // gemm_tile.h's geometry (unit_slot, unit_dst) and fragment read, written out: called through the header from here and from
+    // prefetch_w, the instruction stream of all four kernels moves (profiles/gemm_tile_resources.md)
     const float* a_src[A_ITERS];
 #pragma unroll
     for (int i = 0; i < A_ITERS; ++i) {
@@ -191,13 +182,13 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
                                              (__attribute__((address_space(3))) void*)(Bs + buf * (BN * BK) + (i * 256 + wave_u) * 4), 16, 0, 0);
     };
 
-    // ---- accumulators and fragments (gemm_f32.hip's 16x16 layouts) ---------------------------------------------------------------
+    // ---- accumulators and fragments ----------------------------------------------------------------------------------------------
     f32x4 acc16[NRB * NCB];
 #pragma unroll
     for (int i = 0; i < NRB * NCB; ++i) acc16[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     constexpr int READS = NRB + NCB;
     constexpr int MFMAS = 4 * NRB * NCB;
-    struct Frag { f32x4 a[NRB]; f32x4 b[NCB]; };
+    using Frag = Frag16<NCB>;
     Frag f0, f1;
     auto read_frags = [&](Frag& f, int buf, int ks) {
         const float* as = As + buf * (BM * BK);
@@ -208,15 +199,7 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
 #pragma unroll
         for (int r = 0; r < NRB; ++r) f.a[r] = *reinterpret_cast<const f32x4*>(as + lds_off(r * 16 + li, slot));
     };
-    auto mma_half = [&](const Frag& f) {      // weights on the MFMA "A" side: a lane ends with 4 consecutive output columns
-#pragma unroll
-        for (int r = 0; r < NRB; ++r)
-#pragma unroll
-            for (int c = 0; c < NCB; ++c)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc16[r * NCB + c] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.b[c][j], f.a[r][j], acc16[r * NCB + c], 0, 0, 0);
-    };
+    auto mma_half = [&](const Frag& f) { mma_half16<NCB>(acc16, f); };
 
     // ---- prologue -----------------------------------------------------------------------------------------------------------
     const int nk = p.K / BK;                       // >= 16 here
@@ -239,7 +222,6 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
 
     // ---- epilogue operands (requested at the top of the peeled last chunk: they land under its MFMAs) --------------------------
     const int nw = n0 + wave * WN;
-    struct ColOps { f32x4 bias, g4, b4; };
     constexpr bool RES = (EPI == EPI_BIAS_RES_LN);
     constexpr bool HAS_RES = RES || EPI == EPI_EMBED;      // a per-unit operand from memory: the residual, or the table row of the embedding
     // the last chunk's iteration is peeled (no wait / barrier / prefetch in it, the epilogue's operands requested at its top) for tiles up to
@@ -277,11 +259,9 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
             for_units([&](int i, int, int m, int nb, f32x4) __attribute__((always_inline)) {
                 res[i] = *reinterpret_cast<const f32x4*>(p.R + (size_t)m * p.ldr + nb);
             });
-        if constexpr (EPI == EPI_EMBED)      // gemm_f32.hip load_res: the timestep token's row for token 0, else the positional (or per-row) table
+        if constexpr (EPI == EPI_EMBED)
             for_units([&](int i, int, int m, int nb, f32x4) __attribute__((always_inline)) {
-                const int bidx = m / p.S, tok = m % p.S;
-                const float* tp = (tok == 0) ? p.tab0 + (size_t)bidx * p.ldtab0 + nb : p.tab + (size_t)(p.tab_by_row ? m : tok) * p.ldtab + nb;
-                res[i] = *reinterpret_cast<const f32x4*>(tp);
+                res[i] = *reinterpret_cast<const f32x4*>(embed_table_row(p, m, nb));
             });
     };
 
@@ -356,7 +336,9 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
 
     // ---- epilogue -----------------------------------------------------------------------------------------------------------
     if constexpr (EPI == EPI_BIAS_RES_LN) {
-        // gemm_f32.hip EPI_BIAS_RES_LN, statement for statement (same statistics, same merge tree: bit-identical results)
+        // gemm_f32.hip layernorm_tail (its comments explain the steps), written out over gemm_tile.h's merges and wait policy: called as
+        // a function, whole or its exchange stage alone, it costs encoder_stack_kernel<4> 0.3 - 0.45 % at B = 64
+        // (profiles/gemm_tile_resources.md).  Same statistics, same tags and slots, same merge tree: bit-identical results
 #pragma unroll
         for (int c = 0; c < NCB; ++c)
 #pragma unroll
@@ -366,18 +348,6 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
 #pragma unroll
                 for (int q = 0; q < 4; ++q) a[q] = (a[q] + col[c].bias[q]) + rr[q];
             }
-        typedef unsigned rohm_u2 __attribute__((ext_vector_type(2)));
-        auto merge_swap = [](float& m, float& q2, float n, bool far) __attribute__((always_inline)) {
-            rohm_u2 tm, tq;
-            if (far) { tm = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-                       tq = __builtin_amdgcn_permlane32_swap(__float_as_uint(q2), __float_as_uint(q2), false, false); }
-            else     { tm = __builtin_amdgcn_permlane16_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-                       tq = __builtin_amdgcn_permlane16_swap(__float_as_uint(q2), __float_as_uint(q2), false, false); }
-            const float ma = __uint_as_float(tm[0]), mb = __uint_as_float(tm[1]);
-            const float d = mb - ma;
-            m = 0.5f * (ma + mb);
-            q2 = (__uint_as_float(tq[0]) + __uint_as_float(tq[1])) + 0.5f * n * d * d;
-        };
         float* const part = zone;                       // [4 waves][BM][2]
         constexpr float kLane = (float)(4 * NCB);
 #pragma unroll
@@ -392,8 +362,8 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
             for (int c = 0; c < NCB; ++c)
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { const float d = acc16[r * NCB + c][k] - m; q2 += d * d; }
-            merge_swap(m, q2, kLane, true);
-            merge_swap(m, q2, 2.0f * kLane, false);
+            merge_stats_swap(m, q2, kLane, true);
+            merge_stats_swap(m, q2, 2.0f * kLane, false);
             if (lg == 0) *reinterpret_cast<f32x2*>(part + (wave * BM + r * 16 + li) * 2) = f32x2{m, q2};
         }
         __syncthreads();
@@ -402,22 +372,17 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
         const unsigned tag = (ep28 << 4) | xcc1;
         float* const row_stats = p.row_stats;
         if (tid < BM) {
-            auto merge = [](float ma, float qa, float mb, float qb, float n, float& m, float& q2) __attribute__((always_inline)) {
-                const float d = mb - ma;
-                m = 0.5f * (ma + mb);
-                q2 = (qa + qb) + 0.5f * n * d * d;
-            };
             f32x2 w4[4];
 #pragma unroll
             for (int w = 0; w < 4; ++w) w4[w] = *reinterpret_cast<const f32x2*>(part + (w * BM + tid) * 2);
             float m01, q01, m23, q23, a, b;
-            merge(w4[0][0], w4[0][1], w4[1][0], w4[1][1], (float)WN, m01, q01);
-            merge(w4[2][0], w4[2][1], w4[3][0], w4[3][1], (float)WN, m23, q23);
-            merge(m01, q01, m23, q23, 2.0f * (float)WN, a, b);
+            merge_stats(w4[0][0], w4[0][1], w4[1][0], w4[1][1], (float)WN, m01, q01);
+            merge_stats(w4[2][0], w4[2][1], w4[3][0], w4[3][1], (float)WN, m23, q23);
+            merge_stats(m01, q01, m23, q23, 2.0f * (float)WN, a, b);
             const unsigned pub = (p.fault && tn == 0) ? (tag ^ 0x80000000u) : tag;
             *reinterpret_cast<f32x4*>(row_stats + ((size_t)tn * BM + tid) * 4) = f32x4{a, __uint_as_float(pub), b, __uint_as_float(pub)};
             float mk[8], qk[8];
-            for (int it = 0;; ++it) {
+            for (WaitTurns w;;) {
                 unsigned long long lo[8], hi[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
@@ -444,24 +409,19 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
                     if (!same_xcd) __hip_atomic_store(p.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     break;
                 }
-                __builtin_amdgcn_s_sleep(1);
-                if ((it & 127) == 127 && __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-                if (it > (1 << 19)) {
-                    __hip_atomic_store(p.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    break;
-                }
+                if (w.give_up(p.err, 1u)) break;
             }
             constexpr float kT = (float)BN;
             if (tiles_n > 1) {
-                merge(mk[0], qk[0], mk[1], qk[1], kT, mk[0], qk[0]);
-                if (tiles_n > 2) merge(mk[2], qk[2], mk[3], qk[3], kT, mk[2], qk[2]);
-                if (tiles_n > 4) { merge(mk[4], qk[4], mk[5], qk[5], kT, mk[4], qk[4]); merge(mk[6], qk[6], mk[7], qk[7], kT, mk[6], qk[6]); }
+                merge_stats(mk[0], qk[0], mk[1], qk[1], kT, mk[0], qk[0]);
+                if (tiles_n > 2) merge_stats(mk[2], qk[2], mk[3], qk[3], kT, mk[2], qk[2]);
+                if (tiles_n > 4) { merge_stats(mk[4], qk[4], mk[5], qk[5], kT, mk[4], qk[4]); merge_stats(mk[6], qk[6], mk[7], qk[7], kT, mk[6], qk[6]); }
             }
             if (tiles_n > 2) {
-                merge(mk[0], qk[0], mk[2], qk[2], 2.0f * kT, mk[0], qk[0]);
-                if (tiles_n > 4) merge(mk[4], qk[4], mk[6], qk[6], 2.0f * kT, mk[4], qk[4]);
+                merge_stats(mk[0], qk[0], mk[2], qk[2], 2.0f * kT, mk[0], qk[0]);
+                if (tiles_n > 4) merge_stats(mk[4], qk[4], mk[6], qk[6], 2.0f * kT, mk[4], qk[4]);
             }
-            if (tiles_n > 4) merge(mk[0], qk[0], mk[4], qk[4], 4.0f * kT, mk[0], qk[0]);
+            if (tiles_n > 4) merge_stats(mk[0], qk[0], mk[4], qk[4], 4.0f * kT, mk[0], qk[0]);
             const float mu = mk[0];
             const float var = qk[0] / (float)p.ln_dim;
             *reinterpret_cast<f32x2*>(part + tid * 2) = f32x2{mu, 1.0f / sqrtf(var + p.eps)};
@@ -575,7 +535,7 @@ __device__ __forceinline__ void head_tail_phase(const StackParams& p, const int 
     for (int i = 0; i < A_ITERS; ++i) {
         const int u = tid + i * 256;
         const int row = (u < A_UNITS) ? (u >> 3) : 0;
-        const int slot = (u & 7) ^ ((row >> 1) & 7);
+        const int slot = unit_slot(u, row);
         a_src[i] = p.h + (size_t)(m0 + row) * D + slot * 4;
     }
     const float* w_src[W_ITERS];
@@ -583,24 +543,20 @@ __device__ __forceinline__ void head_tail_phase(const StackParams& p, const int 
     for (int i = 0; i < W_ITERS; ++i) {
         const int u = tid + i * 256;
         const int lrow = (u < W_UNITS) ? (u >> 3) : 0;
-        const int slot = (u & 7) ^ ((lrow >> 1) & 7);
+        const int slot = unit_slot(u, lrow);
         const int grow = (lrow < NC_OWN * 16) ? tn * NC_OWN * 16 + lrow : 256 + (lrow - NC_OWN * 16);
         w_src[i] = p.t_out_w + (size_t)grow * D + slot * 4;
     }
     auto dma = [&](int buf, int k0) {
 #pragma unroll
         for (int i = 0; i < A_ITERS; ++i) {
-            float* dst = smem + buf * kBuf + (i * 256 + wave_u) * 4;
-            if (i == A_ITERS - 1 && A_UNITS % 256 != 0)
-                dst = (wave_u < A_UNITS - (A_ITERS - 1) * 256) ? dst : lds_dummy + (wave_u & 64) * 4;
+            float* const dst = unit_dst<A_UNITS>(smem + buf * kBuf, i, wave_u, lds_dummy);
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_src[i] + k0),
                                              (__attribute__((address_space(3))) void*)dst, 16, 0, kSc1);
         }
 #pragma unroll
         for (int i = 0; i < W_ITERS; ++i) {
-            float* dst = smem + buf * kBuf + BM * BK + (i * 256 + wave_u) * 4;
-            if (i == W_ITERS - 1 && W_UNITS % 256 != 0)
-                dst = (wave_u < W_UNITS - (W_ITERS - 1) * 256) ? dst : lds_dummy + (wave_u & 64) * 4;
+            float* const dst = unit_dst<W_UNITS>(smem + buf * kBuf + BM * BK, i, wave_u, lds_dummy);
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w_src[i] + k0),
                                              (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
         }
@@ -767,7 +723,7 @@ __global__ __launch_bounds__(256) void encoder_chain_kernel(ChainParams p) {
     const int x = blockIdx.x % kNumXCD, j = blockIdx.x / kNumXCD;
     const int g = (j / G) * kNumXCD + x, tn = j % G;
     if (g >= p.tiles_m) return;
-    const unsigned xcc1 = 1u + (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20);
+    const unsigned xcc1 = xcd_id1();
     const unsigned ep = p.epoch + 64u * *p.xln_pass;      // the pass counter was advanced by an EARLIER kernel of the stream
     if (tid == 0) p.xln_xcc[g * 8 + tn] = xcc1;
     unsigned long long* const flags = p.flags + (size_t)g * 9 * 5 * 8;
@@ -817,7 +773,7 @@ __global__ __launch_bounds__(256) void encoder_stack_kernel(StackParams p) {
     const int x = blockIdx.x % kNumXCD, j = blockIdx.x / kNumXCD;
     const int g = (j / G) * kNumXCD + x, tn = j % G;
     if (g >= p.tiles_m) return;
-    const unsigned xcc1 = 1u + (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20);
+    const unsigned xcc1 = xcd_id1();
     const unsigned ep = p.epoch + 64u * (*p.xln_pass + p.pass_add);
     if (tid0 == 0) p.xln_xcc[g * 8 + tn] = xcc1;
 

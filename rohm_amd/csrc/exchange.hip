@@ -14,6 +14,7 @@
 #include <unistd.h>
 #include <mutex>
 #include "common.h"
+#include "gemm_tile.h"
 
 namespace rohm {
 
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void exchange_probe_kernel(unsigned* buf) {   
     extern __shared__ float probe_pad[];
     if (threadIdx.x != 0) return;
     probe_pad[0] = 0.f;
-    buf[1 + blockIdx.x] = 1u + (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20);
+    buf[1 + blockIdx.x] = xcd_id1();
     __hip_atomic_fetch_add(buf, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     unsigned ok = 0u;
     for (int it = 0; it < (1 << 15); ++it) {      // ~20 ms at the outside

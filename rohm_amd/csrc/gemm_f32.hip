@@ -37,18 +37,150 @@
 #include <type_traits>
 #include <string.h>
 #include "common.h"
-#include "gemm_sched.h"
+#include "gemm_tile.h"
 
 namespace rohm {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int BM = 144;
-constexpr int BK = 32;
-constexpr int NRB = BM / 16;        // 9 row blocks of 16 (BN = 64 path)
+using namespace gemm_tile;         // BM = 144, BK = 32, NRB = 9 row blocks of 16 (BN = 64 path), the staging geometry, the 16x16 fragments
 constexpr int kSkWorkgroups = 256;  // stream-K launches: one workgroup per CU (32 per XCD)
-constexpr int A_UNITS = BM * 8;     // 16-byte units per A chunk (1152)
-constexpr int A_ITERS = (A_UNITS + 255) / 256;  // 5 (the last pass is half populated)
+
+// ---- the LayerNorm tail of EPI_BIAS_RES_LN: C = LayerNorm(acc + bias + R) of a 144 x BN tile whose row spans tiles_n column tiles ------
+// The exchange operands of one tile of the LayerNorm tail.
+struct LnExchange {
+    float* row_stats;        // this ROW tile's slots: [tiles_n column tiles][BM rows] x 16 bytes (mean, tag, M2, tag)
+    int tn, tiles_n;         // this tile's column-tile index; tiles_n is 1, 2, 4 or 8
+    unsigned ep28;           // the launch's (phase's) 28-bit tag
+    unsigned xcc1;           // xcd_id1() of this workgroup
+    int fault;               // test hook (rohm_posenet_inject_exchange_fault): column tile 0 publishes under a tag nobody waits for
+    unsigned* err;           // the error word: 1 = a wait expired, 2 = a partner published from another XCD
+};
+
+// acc16 / res / col: the lane's accumulators (16x16 layouts: acc16[r * NCB + c][q] = C[m0 + 16 r + li][nw + 16 c + 4 lg + q]), residuals
+// (res[c * NRB + r]) and column operands.  part: 4 * BM * 2 floats of LDS.  Every thread of the workgroup calls it (two barriers).
+// p.ln_dim, p.ln_eps, p.C, p.ldc are read where they are used.  (gemm_phase of encoder_chain.hip writes the same tail out: called from
+// there, this function costs encoder_stack_kernel<4> 0.3 - 0.45 %, profiles/gemm_tile_resources.md.)
+template <int BN, int NCB>
+__device__ __forceinline__ void layernorm_tail(f32x4 (&acc16)[NRB * NCB], const f32x4 (&res)[NCB * NRB], const ColOps (&col)[NCB], float* const part,
+                                               const int tid, const int wave, const int li, const int lg, const LnExchange& x, const GemmParams& p,
+                                               const int m0, const int nw) {
+    constexpr int WN = BN / 4;
+    static_assert(NCB == WN / 16, "layernorm_tail: a wave owns BN / 4 columns");
+    // 1. x = (acc + bias) + R in the accumulator registers (the order of the un-fused path)
+#pragma unroll
+    for (int c = 0; c < NCB; ++c)
+#pragma unroll
+        for (int r = 0; r < NRB; ++r) {
+            f32x4& a = acc16[r * NCB + c];
+            const f32x4 rr = res[c * NRB + r];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a[q] = (a[q] + col[c].bias[q]) + rr[q];
+        }
+    // 2. row statistics as (mean, M2) of equal-sized parts, merged pairwise by Chan's update at every level: the lane's own 4 NCB
+    //    columns (two-pass in registers), the 4 lanes li + 16 lg of a row (two lane swaps on the VALU), the 4 waves (LDS), the partner
+    //    tiles (L2).  As stable as nn.LayerNorm's own two-pass kernel -- no E[x^2] - mu^2 cancellation for rows far from zero -- at the
+    //    price of a few VALU operations, no extra barrier.
+    //    part: [4 waves][BM][2] (mean, M2) of a wave's columns; afterwards [BM][2] = (mu, rstd)
+    constexpr float kLane = (float)(4 * NCB);       // elements per lane and row
+#pragma unroll
+    for (int r = 0; r < NRB; ++r) {
+        float sm = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCB; ++c)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sm += acc16[r * NCB + c][k];
+        float m = sm * (1.0f / kLane), q2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCB; ++c)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const float d = acc16[r * NCB + c][k] - m; q2 += d * d; }
+        merge_stats_swap(m, q2, kLane, true);             // lanes l and l ^ 32
+        merge_stats_swap(m, q2, 2.0f * kLane, false);     // ... and l ^ 16: the wave's WN columns of the row
+        if (lg == 0) *reinterpret_cast<f32x2*>(part + (wave * BM + r * 16 + li) * 2) = f32x2{m, q2};
+    }
+    __syncthreads();
+    // 3. publish this tile's (mean, M2) of every row and collect the partner tiles'.  A slot is 16 bytes (mean, tag, M2, tag)
+    //    written by ONE store: each 8-byte half carries the launch's tag, so a reader that sees both tags has the data (no
+    //    separate flag, no wait for the store's acknowledgement, no counter to re-arm: three dependent trips to L2 less than
+    //    publish / count / poll).  tag = (epoch of the launch, 28 bits) << 4 | (XCD id + 1): never 0, so zeroed memory is stale.
+    //    Tiles are merged in a fixed tree over the column-tile index with the own pair taken from registers at its place: every
+    //    tile of the row gets bit-identical statistics whatever the arrival order.
+    const int tn = x.tn, tiles_n = x.tiles_n;
+    const unsigned xcc1 = x.xcc1, ep28 = x.ep28;
+    const unsigned tag = (ep28 << 4) | xcc1;
+    float* const row_stats = x.row_stats;
+    if (tid < BM) {
+        f32x2 w4[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) w4[w] = *reinterpret_cast<const f32x2*>(part + (w * BM + tid) * 2);
+        float m01, q01, m23, q23, a, b;
+        merge_stats(w4[0][0], w4[0][1], w4[1][0], w4[1][1], (float)WN, m01, q01);
+        merge_stats(w4[2][0], w4[2][1], w4[3][0], w4[3][1], (float)WN, m23, q23);
+        merge_stats(m01, q01, m23, q23, 2.0f * (float)WN, a, b);                     // this tile's BN columns of row tid
+        const unsigned pub = (x.fault && tn == 0) ? (tag ^ 0x80000000u) : tag;
+        *reinterpret_cast<f32x4*>(row_stats + ((size_t)tn * BM + tid) * 4) = f32x4{a, __uint_as_float(pub), b, __uint_as_float(pub)};
+        float mk[8], qk[8];
+        for (WaitTurns w;;) {
+            unsigned long long lo[8], hi[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                lo[k] = hi[k] = 0ull;
+                if (k < tiles_n && k != tn) {          // past the L1: the partner's store went to L2
+                    const unsigned long long* sp = reinterpret_cast<const unsigned long long*>(row_stats + ((size_t)k * BM + tid) * 4);
+                    lo[k] = __hip_atomic_load(sp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    hi[k] = __hip_atomic_load(sp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+            bool ok = true, same_xcd = true;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                mk[k] = 0.f; qk[k] = 0.f;
+                if (k >= tiles_n) continue;
+                if (k == tn) { mk[k] = a; qk[k] = b; continue; }
+                const unsigned tl = (unsigned)(lo[k] >> 32), th = (unsigned)(hi[k] >> 32);
+                ok = ok && (tl >> 4) == ep28 && (th >> 4) == ep28 && (tl & 15u) != 0u && (th & 15u) != 0u;
+                same_xcd = same_xcd && (tl & 15u) == xcc1 && (th & 15u) == xcc1;
+                mk[k] = __uint_as_float((unsigned)lo[k]);
+                qk[k] = __uint_as_float((unsigned)hi[k]);
+            }
+            if (ok) {
+                if (!same_xcd) __hip_atomic_store(x.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                break;
+            }
+            if (w.give_up(x.err, 1u)) break;
+        }
+        // a balanced tree over the tile index (static indices: the arrays stay in registers)
+        constexpr float kT = (float)BN;
+        if (tiles_n > 1) {
+            merge_stats(mk[0], qk[0], mk[1], qk[1], kT, mk[0], qk[0]);
+            if (tiles_n > 2) merge_stats(mk[2], qk[2], mk[3], qk[3], kT, mk[2], qk[2]);
+            if (tiles_n > 4) { merge_stats(mk[4], qk[4], mk[5], qk[5], kT, mk[4], qk[4]); merge_stats(mk[6], qk[6], mk[7], qk[7], kT, mk[6], qk[6]); }
+        }
+        if (tiles_n > 2) {
+            merge_stats(mk[0], qk[0], mk[2], qk[2], 2.0f * kT, mk[0], qk[0]);
+            if (tiles_n > 4) merge_stats(mk[4], qk[4], mk[6], qk[6], 2.0f * kT, mk[4], qk[4]);
+        }
+        if (tiles_n > 4) merge_stats(mk[0], qk[0], mk[4], qk[4], 4.0f * kT, mk[0], qk[0]);
+        const float mu = mk[0];
+        const float var = qk[0] / (float)p.ln_dim;
+        *reinterpret_cast<f32x2*>(part + tid * 2) = f32x2{mu, 1.0f / sqrtf(var + p.ln_eps)};      // own row of wave 0's zone: read above
+    }
+    __syncthreads();
+    // 4. normalise in registers, store LN(x) once
+#pragma unroll
+    for (int r = 0; r < NRB; ++r) {
+        const f32x2 mrv = *reinterpret_cast<const f32x2*>(part + (r * 16 + li) * 2);
+#pragma unroll
+        for (int c = 0; c < NCB; ++c) {
+            const f32x4 a = acc16[r * NCB + c];
+            f32x4 v;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = (a[q] - mrv[0]) * mrv[1] * col[c].g4[q] + col[c].b4[q];
+            *reinterpret_cast<f32x4*>(p.C + (size_t)(m0 + r * 16 + li) * p.ldc + nw + c * 16 + lg * 4) = v;
+        }
+    }
+}
 
 template <int BN, int EPI, bool FULL = false, bool CONV = false>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
@@ -174,7 +306,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     for (int i = 0; i < A_ITERS; ++i) {
         const int u = tid + i * 256;
         const int row = (u < A_UNITS) ? (u >> 3) : 0;
-        const int slot = (u & 7) ^ ((row >> 1) & 7);
+        const int slot = unit_slot(u, row);
         const int grow = (m0 + row < p.M) ? m0 + row : p.M - 1;
         a_src[i] = p.A + (size_t)grow * p.lda + slot * 4;
         if constexpr (CONV) {
@@ -207,19 +339,15 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     for (int i = 0; i < B_ITERS; ++i) {
         const int u = tid + i * 256;
         const int row = u >> 3;
-        const int slot = (u & 7) ^ ((row >> 1) & 7);
+        const int slot = unit_slot(u, row);
         const int grow = (n0 + row < p.N) ? n0 + row : p.N - 1;
         b_src[i] = p.W + (size_t)grow * p.ldw + slot * 4;
     }
     auto dma_piece = [&](int piece, int buf, int k0) {
         if (piece < A_ITERS) {
-            // the last A pass is half populated: waves 2-3 fetch a (valid) dummy row into the landing zone instead
-            // of being predicated off -- a branch here would split the block the scheduler interleaves
-            float* dst = As + buf * (BM * BK) + (piece * 256 + wave_u) * 4;
-            if (piece == A_ITERS - 1 && A_UNITS % 256 != 0)
-                dst = (wave_u < A_UNITS - (A_ITERS - 1) * 256) ? dst : lds_dummy + (wave_u & 64) * 4;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(CONV ? conv_src(piece, k0) : a_src[piece] + k0),
-                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+                                             (__attribute__((address_space(3))) void*)unit_dst<A_UNITS>(As + buf * (BM * BK), piece, wave_u, lds_dummy),
+                                             16, 0, 0);
         } else {
             const int i = piece - A_ITERS;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_src[i] + k0),
@@ -252,7 +380,8 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     constexpr int FB = M32 ? 2 * NCB32 + NCB : NCB;
     constexpr int READS = FA + FB;
     constexpr int MFMAS = M32 ? 32 * NCB32 + 4 * NCB : 4 * NRB * NCB;
-    struct Frag { f32x4 a[FA]; f32x4 b[FB]; };
+    struct Frag32 { f32x4 a[FA]; f32x4 b[FB]; };
+    using Frag = std::conditional_t<M32, Frag32, Frag16<NCB>>;
     Frag f0, f1;
     auto read_frags = [&](Frag& f, int buf, int ks) {
         const float* as = As + buf * (BM * BK);
@@ -273,7 +402,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
 #pragma unroll
             for (int c = 0; c < NCB; ++c)
                 f.b[2 * NCB32 + c] = *reinterpret_cast<const f32x4*>(bs + lds_off(c * 16 + li, slot16));
-        } else {
+        } else {      // (written out: as a function of gemm_tile.h it moves every 16x16 kernel's schedule, profiles/gemm_tile_resources.md)
             const int slot = ks * 4 + lg;
 #pragma unroll
             for (int c = 0; c < NCB; ++c) f.b[c] = *reinterpret_cast<const f32x4*>(bs + lds_off(c * 16 + li, slot));
@@ -306,17 +435,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
                     else acc16[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, wv, acc16[c], 0, 0, 0);
                 }
         } else {
-#pragma unroll
-            for (int r = 0; r < NRB; ++r)
-#pragma unroll
-                for (int c = 0; c < NCB; ++c)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if constexpr (SWAP)
-                            acc16[r * NCB + c] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.b[c][j], f.a[r][j], acc16[r * NCB + c], 0, 0, 0);
-                        else
-                            acc16[r * NCB + c] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[r][j], f.b[c][j], acc16[r * NCB + c], 0, 0, 0);
-                    }
+            mma_half16<NCB, SWAP>(acc16, f);
         }
     };
 
@@ -355,7 +474,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     // dependent round trip to memory per unit (18 to 54 per lane).  The hot instantiations (PRE) therefore read the operands of
     // ALL units first (identical addresses -- the bias of a column group -- collapse into one load) and then only compute
     // and store.
-    struct ColOps { f32x4 bias, g4, b4; };          // what depends on the column group only
     // (not where it would spill: the 384-wide tile keeps 216 accumulators per lane; its QKV form fits, 475 VGPRs)
     constexpr bool RES = (EPI == EPI_BIAS_RES || EPI == EPI_BIAS_RES_LN);      // epilogues that add R[m][n]
     constexpr bool PRE = !(BN >= 384 && (EPI == EPI_BIAS || RES || EPI == EPI_EMBED));
@@ -383,8 +501,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
         f32x4 rr = zero4;
         if constexpr (EPI == EPI_EMBED) {      // the row of the positional / timestep table this unit adds
             if (!FULL && (m >= p.M || nb >= p.N)) return rr;
-            const int bidx = m / p.S, tok = m % p.S;
-            const float* tp = (tok == 0) ? p.tab0 + (size_t)bidx * p.ldtab0 + nb : p.tab + (size_t)(p.tab_by_row ? m : tok) * p.ldtab + nb;
+            const float* tp = embed_table_row(p, m, nb);
             if constexpr (FULL) {
                 rr = *reinterpret_cast<const f32x4*>(tp);
             } else {
@@ -542,149 +659,12 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
         // C = LayerNorm(acc + bias + R): see GemmParams::xln_*.  FULL, 16x16 layouts (BN <= 128) only -- the launcher sees to it.
         static_assert(!M32 && !CONV && FULL && PRE, "EPI_BIAS_RES_LN: 144 x 64 / 144 x 128 tiles of whole problems only");
         if constexpr (!EARLY) request_ops();
-        // 1. x = (acc + bias) + R in the accumulator registers (the order of the un-fused path)
-#pragma unroll
-        for (int c = 0; c < NCB; ++c)
-#pragma unroll
-            for (int r = 0; r < NRB; ++r) {
-                f32x4& a = acc16[r * NCB + c];
-                const f32x4 rr = res[c * NRB + r];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) a[q] = (a[q] + col[c].bias[q]) + rr[q];
-            }
-        // 2. row statistics as (mean, M2 = sum of squares about that mean) of equal-sized parts, merged pairwise by Chan's update
-        //        mean = (m_a + m_b) / 2,   M2 = M2_a + M2_b + n (m_b - m_a)^2 / 2        (n = elements per part)
-        //    at every level: the lane's own 4 NCB columns (two-pass in registers), the 4 lanes li + 16 lg of a row (two lane swaps on
-        //    the VALU), the 4 waves (LDS), the partner tiles (L2).  As stable as nn.LayerNorm's own two-pass kernel -- no
-        //    E[x^2] - mu^2 cancellation for rows far from zero -- at the price of a few VALU operations, no extra barrier.
-        typedef unsigned rohm_u2 __attribute__((ext_vector_type(2)));
-        auto merge_swap = [](float& m, float& q2, float n, bool far) __attribute__((always_inline)) {
-            rohm_u2 tm, tq;
-            if (far) { tm = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-                       tq = __builtin_amdgcn_permlane32_swap(__float_as_uint(q2), __float_as_uint(q2), false, false); }
-            else     { tm = __builtin_amdgcn_permlane16_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-                       tq = __builtin_amdgcn_permlane16_swap(__float_as_uint(q2), __float_as_uint(q2), false, false); }
-            const float ma = __uint_as_float(tm[0]), mb = __uint_as_float(tm[1]);
-            const float d = mb - ma;
-            m = 0.5f * (ma + mb);
-            q2 = (__uint_as_float(tq[0]) + __uint_as_float(tq[1])) + 0.5f * n * d * d;
-        };
-        float* const part = lds_dummy + 512;            // [4 waves][BM][2] (mean, M2) of a wave's columns; afterwards [BM][2] = (mu, rstd)
-        constexpr float kLane = (float)(4 * NCB);       // elements per lane and row
-#pragma unroll
-        for (int r = 0; r < NRB; ++r) {
-            float sm = 0.f;
-#pragma unroll
-            for (int c = 0; c < NCB; ++c)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) sm += acc16[r * NCB + c][k];
-            float m = sm * (1.0f / kLane), q2 = 0.f;
-#pragma unroll
-            for (int c = 0; c < NCB; ++c)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { const float d = acc16[r * NCB + c][k] - m; q2 += d * d; }
-            merge_swap(m, q2, kLane, true);             // lanes l and l ^ 32
-            merge_swap(m, q2, 2.0f * kLane, false);     // ... and l ^ 16: the wave's WN columns of the row
-            if (lg == 0) *reinterpret_cast<f32x2*>(part + (wave * BM + r * 16 + li) * 2) = f32x2{m, q2};
-        }
-        __syncthreads();
+        // which XCD this tile ran on: recorded for the tests
         const int g = m0 / BM, tn = n0 / BN;
-        // which XCD this tile ran on: recorded for the tests, and part of the tag -- a partner that publishes from another XCD is
-        // reported (status 2), not trusted silently
-        const unsigned xcc1 = 1u + (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20);      // 1 .. 8
+        const unsigned xcc1 = xcd_id1();
         if (tid == 0) p.xln_xcc[g * 8 + tn] = xcc1;
-        // 3. publish this tile's (mean, M2) of every row and collect the partner tiles'.  A slot is 16 bytes (mean, tag, M2, tag)
-        //    written by ONE store: each 8-byte half carries the launch's tag, so a reader that sees both tags has the data (no
-        //    separate flag, no wait for the store's acknowledgement, no counter to re-arm: three dependent trips to L2 less than
-        //    publish / count / poll).  tag = (epoch of the launch, 28 bits) << 4 | (XCD id + 1): never 0, so zeroed memory is stale.
-        //    Tiles are merged in a fixed tree over the column-tile index with the own pair taken from registers at its place: every
-        //    tile of the row gets bit-identical statistics whatever the arrival order.
-        float* const row_stats = p.xln_stats + ((size_t)g * tiles_n * BM) * 4;
-        const unsigned ep28 = xln_ep & 0x0fffffffu;
-        const unsigned tag = (ep28 << 4) | xcc1;
-        if (tid < BM) {
-            auto merge = [](float ma, float qa, float mb, float qb, float n, float& m, float& q2) __attribute__((always_inline)) {
-                const float d = mb - ma;
-                m = 0.5f * (ma + mb);
-                q2 = (qa + qb) + 0.5f * n * d * d;
-            };
-            f32x2 w4[4];
-#pragma unroll
-            for (int w = 0; w < 4; ++w) w4[w] = *reinterpret_cast<const f32x2*>(part + (w * BM + tid) * 2);
-            float m01, q01, m23, q23, a, b;
-            merge(w4[0][0], w4[0][1], w4[1][0], w4[1][1], (float)WN, m01, q01);
-            merge(w4[2][0], w4[2][1], w4[3][0], w4[3][1], (float)WN, m23, q23);
-            merge(m01, q01, m23, q23, 2.0f * (float)WN, a, b);                     // this tile's BN columns of row tid
-            // (test hook, rohm_posenet_inject_exchange_fault: column tile 0 publishes under a tag nobody waits for)
-            const unsigned pub = (p.xln_fault && tn == 0) ? (tag ^ 0x80000000u) : tag;
-            *reinterpret_cast<f32x4*>(row_stats + ((size_t)tn * BM + tid) * 4) = f32x4{a, __uint_as_float(pub), b, __uint_as_float(pub)};
-            float mk[8], qk[8];
-            for (int it = 0;; ++it) {
-                unsigned long long lo[8], hi[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    lo[k] = hi[k] = 0ull;
-                    if (k < tiles_n && k != tn) {          // past the L1: the partner's store went to L2
-                        const unsigned long long* sp = reinterpret_cast<const unsigned long long*>(row_stats + ((size_t)k * BM + tid) * 4);
-                        lo[k] = __hip_atomic_load(sp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        hi[k] = __hip_atomic_load(sp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-                bool ok = true, same_xcd = true;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    mk[k] = 0.f; qk[k] = 0.f;
-                    if (k >= tiles_n) continue;
-                    if (k == tn) { mk[k] = a; qk[k] = b; continue; }
-                    const unsigned tl = (unsigned)(lo[k] >> 32), th = (unsigned)(hi[k] >> 32);
-                    ok = ok && (tl >> 4) == ep28 && (th >> 4) == ep28 && (tl & 15u) != 0u && (th & 15u) != 0u;
-                    same_xcd = same_xcd && (tl & 15u) == xcc1 && (th & 15u) == xcc1;
-                    mk[k] = __uint_as_float((unsigned)lo[k]);
-                    qk[k] = __uint_as_float((unsigned)hi[k]);
-                }
-                if (ok) {
-                    if (!same_xcd) __hip_atomic_store(p.xln_err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-                // a wait that another launch of this pass (or an earlier row) already lost is not worth 0.2 s again: the results since
-                // the last status check are void anyway, the host falls back and re-runs (rohm_amd/diffusion/ddpm.py)
-                if ((it & 127) == 127 && __hip_atomic_load(p.xln_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-                if (it > (1 << 19)) {                   // ~0.2 s: never on a healthy device (the partner tiles are co-resident); do not hang it
-                    __hip_atomic_store(p.xln_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    break;
-                }
-            }
-            // tiles_n is 1, 2, 4 or 8: a balanced tree over the tile index (static indices: the arrays stay in registers)
-            constexpr float kT = (float)BN;
-            if (tiles_n > 1) {
-                merge(mk[0], qk[0], mk[1], qk[1], kT, mk[0], qk[0]);
-                if (tiles_n > 2) merge(mk[2], qk[2], mk[3], qk[3], kT, mk[2], qk[2]);
-                if (tiles_n > 4) { merge(mk[4], qk[4], mk[5], qk[5], kT, mk[4], qk[4]); merge(mk[6], qk[6], mk[7], qk[7], kT, mk[6], qk[6]); }
-            }
-            if (tiles_n > 2) {
-                merge(mk[0], qk[0], mk[2], qk[2], 2.0f * kT, mk[0], qk[0]);
-                if (tiles_n > 4) merge(mk[4], qk[4], mk[6], qk[6], 2.0f * kT, mk[4], qk[4]);
-            }
-            if (tiles_n > 4) merge(mk[0], qk[0], mk[4], qk[4], 4.0f * kT, mk[0], qk[0]);
-            const float mu = mk[0];
-            const float var = qk[0] / (float)p.ln_dim;
-            *reinterpret_cast<f32x2*>(part + tid * 2) = f32x2{mu, 1.0f / sqrtf(var + p.ln_eps)};      // own row of wave 0's zone: read above
-        }
-        __syncthreads();
-        // 4. normalise in registers, store LN(x) once
-#pragma unroll
-        for (int r = 0; r < NRB; ++r) {
-            const f32x2 mrv = *reinterpret_cast<const f32x2*>(part + (r * 16 + li) * 2);
-#pragma unroll
-            for (int c = 0; c < NCB; ++c) {
-                const f32x4 a = acc16[r * NCB + c];
-                f32x4 v;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = (a[q] - mrv[0]) * mrv[1] * col[c].g4[q] + col[c].b4[q];
-                *reinterpret_cast<f32x4*>(p.C + (size_t)(m0 + r * 16 + li) * p.ldc + nw + c * 16 + lg * 4) = v;
-            }
-        }
+        const LnExchange x{p.xln_stats + ((size_t)g * tiles_n * BM) * 4, tn, tiles_n, xln_ep & 0x0fffffffu, xcc1, p.xln_fault, p.xln_err};
+        layernorm_tail<BN, NCB>(acc16, res, col, lds_dummy + 512, tid, wave, li, lg, x, p, m0, nw);
     } else if constexpr (EPI == EPI_OUT_T) {
         if constexpr (SK) {
             constexpr size_t kSlot = (size_t)N16 * 256 * 4;        // floats per workgroup slot: accumulator i of thread t at (i * 256 + t) * 4
@@ -697,7 +677,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
                 if (tid == 0) {
-                    const unsigned long long xcc = 1u + (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20);
+                    const unsigned long long xcc = xcd_id1();
                     __hip_atomic_store(p.sk_flag + blockIdx.x, (xcc << 32) | xln_ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 continue;
@@ -709,22 +689,14 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
                 for (int jb = (int)(blockIdx.x / kNumXCD) - 1; jb >= 0 && (jb + 1) * p.sk_units > tile_u0; --jb) {
                     const unsigned src = (unsigned)jb * kNumXCD + blockIdx.x % kNumXCD;
                     if (tid == 0) {
-                        const unsigned long long xcc = 1u + (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20);
-                        for (int it = 0;; ++it) {
-                            const unsigned long long f = __hip_atomic_load(p.sk_flag + src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            if ((unsigned)f == xln_ep && (f >> 32) != 0ull) {      // (XCD id + 1 is never 0: zeroed memory is stale)
-                                // a producer on another XCD would have left its partial in another L2: never with the hardware's
-                                // round-robin placement, and not survivable silently
-                                if ((f >> 32) != xcc) __hip_atomic_store(p.xln_err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                break;
-                            }
-                            __builtin_amdgcn_s_sleep(1);
-                            if ((it & 127) == 127 && __hip_atomic_load(p.xln_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-                            if (it > (1 << 19)) {                   // ~0.2 s: do not hang the device; the host reads the word
-                                __hip_atomic_store(p.xln_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                break;
-                            }
-                        }
+                        const unsigned long long xcc = xcd_id1();
+                        wait_word(p.sk_flag + src, [&](unsigned long long f) __attribute__((always_inline)) {
+                            if (!((unsigned)f == xln_ep && (f >> 32) != 0ull)) return false;      // (XCD id + 1 is never 0: zeroed memory is stale)
+                            // a producer on another XCD would have left its partial in another L2: never with the hardware's
+                            // round-robin placement, and not survivable silently
+                            if ((f >> 32) != xcc) __hip_atomic_store(p.xln_err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            return true;
+                        }, p.xln_err, 1u);
                     }
                     __syncthreads();
                     const unsigned long long* slot = reinterpret_cast<const unsigned long long*>(p.sk_part + (size_t)src * kSlot);

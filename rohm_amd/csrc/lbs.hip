@@ -22,7 +22,7 @@
 #include <vector>
 #include <type_traits>
 #include "common.h"
-#include "gemm_sched.h"
+#include "gemm_tile.h"
 #include "smplx_fk.h"
 
 namespace rohm {
@@ -150,7 +150,6 @@ __global__ __launch_bounds__(64) void lbs_finish_pose_kernel(const float* __rest
 // posed vertices p of the next tile are requested before the MFMAs of this one.  LDS images are [rows][32] per K chunk with the
 // gemm_f32 swizzle (applied on the per-lane SOURCE address; the DMA writes lane-linear): conflict-free ds_read_b128 fragments.
 constexpr int SKIN_BM = 144, SKIN_BN = 192;
-__device__ __forceinline__ int skin_lds_off(int row, int slot) { return row * 32 + ((slot ^ ((row >> 1) & 7)) << 2); }
 
 __global__ __launch_bounds__(256) void lbs_skin_mfma_kernel(const float* __restrict__ Wp, const float* __restrict__ Tm,
                                                             const float* __restrict__ vposed, int ldv,
@@ -171,7 +170,7 @@ __global__ __launch_bounds__(256) void lbs_skin_mfma_kernel(const float* __restr
         for (int u0 = 0; u0 < rows * 8; u0 += 256) {            // rows * 8 is a multiple of 256 for 192 rows; 144 rows: 4.5 passes
             const int u = u0 + tid;
             const int row = (u < rows * 8) ? (u >> 3) : 0;
-            const int slot = (u & 7) ^ ((row >> 1) & 7);
+            const int slot = gemm_tile::unit_slot(u, row);
             const bool live = (u0 + wave_u) < rows * 8;                                   // wave-uniform (rows * 8 % 64 == 0)
 #pragma unroll
             for (int ch = 0; ch < 2; ++ch) {
@@ -249,9 +248,9 @@ __global__ __launch_bounds__(256) void lbs_skin_mfma_kernel(const float* __restr
         auto skin_read = [&](SkinFrag& fr, int step) __attribute__((always_inline)) {
             const int ch = step >> 1, slot = (step & 1) * 4 + lg;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) fr.b[c] = *reinterpret_cast<const f32x4*>(Bs + ch * SKIN_BN * 32 + skin_lds_off(wave * 48 + c * 16 + li, slot));
+            for (int c = 0; c < 3; ++c) fr.b[c] = *reinterpret_cast<const f32x4*>(Bs + ch * SKIN_BN * 32 + lds_off(wave * 48 + c * 16 + li, slot));
 #pragma unroll
-            for (int r = 0; r < 9; ++r) fr.a[r] = *reinterpret_cast<const f32x4*>(as + ch * SKIN_BM * 32 + skin_lds_off(r * 16 + li, slot));
+            for (int r = 0; r < 9; ++r) fr.a[r] = *reinterpret_cast<const f32x4*>(as + ch * SKIN_BM * 32 + lds_off(r * 16 + li, slot));
         };
         auto skin_mma = [&](const SkinFrag& fr) __attribute__((always_inline)) {
 #pragma unroll

@@ -36,6 +36,7 @@
 #include <type_traits>
 #include <vector>
 #include "trajnet_priv.h"
+#include "gemm_tile.h"
 
 namespace rohm {
 namespace res {
@@ -114,12 +115,10 @@ __device__ __forceinline__ f32x4 ld16_l2(const float* p) {      // 16 bytes anot
 // error word: low byte 1 = a bounded wait expired, 2 = a partner published from another XCD; bits 8.. = where (meeting index, or
 // 0x80 | layer index for a statistics exchange)
 __device__ __forceinline__ bool wait_tag(const unsigned long long* p, unsigned tag, unsigned* err, unsigned where, unsigned long long* out) {
-    for (int it = 0;; ++it) {
+    for (WaitTurns w;;) {
         const unsigned long long f = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if ((unsigned)(f >> 32) == tag) { *out = f; return true; }
-        __builtin_amdgcn_s_sleep(1);
-        if ((it & 127) == 127 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return false;
-        if (it > (1 << 19)) { __hip_atomic_store(err, 1u | (where << 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return false; }
+        if (w.give_up(err, 1u | (where << 8))) return false;
     }
 }
 
@@ -570,7 +569,7 @@ __global__ __launch_bounds__(256) void traj_resident_kernel(RParams p) {
     const int c_lo = xcd * p.n_per_xcd, nx = min(p.B - c_lo, p.n_per_xcd);
     if (nx <= 0) return;
     if (__hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;      // an earlier step's wait expired: the host re-runs the loop
-    const unsigned xcc1 = 1u + (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20);
+    const unsigned xcc1 = xcd_id1();
     // The layer records come from memory ONCE per launch, all of them in one round trip, into LDS: read one by one where they are used,
     // every layer started with ~1.4 us of scalar-load latency (a launch begins with cold caches; profiles/r6_u_*)
     unsigned* const lds_ops = reinterpret_cast<unsigned*>(smem + kStage + 1536);
