@@ -66,6 +66,12 @@
  *   - handles are immutable after create (documented exceptions, all control calls that must not race with
  *     launches of the same handle: rohm_posenet_set_exchange, rohm_posenet_inject_exchange_fault,
  *     rohm_posenet_set_stack_timeline); calls are re-entrant across streams given distinct workspaces.
+ *     Every Python binding that keeps a workspace hands out one per HIP stream (PoseNet, TrajNet, and the SMPL-X layer's guidance
+ *     and skinning scratch); every other wrapper allocates per call.  One limit: the stream-K output head and the clip-resident
+ *     TrajNet step launch 256 one-per-CU workgroups that meet through L2, so two of them in flight on two streams cannot both be
+ *     resident and one may report an expired wait (ROHM_ERR_EXCHANGE; the loop falls back to its launch-per-layer form) -- run
+ *     those launches one at a time per device.  tests/test_gpu_reentrancy.py holds every entry point to this (a ledger of who was
+ *     handed which memory; two streams released together; two host threads on one handle).
  *     One handle per device.
  *
  * Caller-owned memory

@@ -41,21 +41,27 @@ class _NativeSMPLX:
                                                     ptr(lw)), 'rohm_smplx_set_skinning')
                 self.has_lbs = True
             self.num_verts, self.num_joints = vt.shape[0], jr.shape[0]
-        self._ws = None
-        self._lbs_ws = None
+        self._ws = {}
+        self._lbs_ws = {}
+
+    def _per_stream(self, cache, n):
+        """The current stream's buffer of `cache`, at least `n` bytes: one per HIP stream, as `_NativePoseNet.workspace` (the
+        library's calls are re-entrant across streams only given distinct workspaces).  A stream's buffer is replaced only by a call
+        made on that stream, and torch's allocator hands a block back to the stream it was allocated on: no other stream's launch
+        can still be using what is dropped here."""
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        ws = cache.get(key)
+        if ws is None or ws.numel() < n:
+            cache.pop(key, None)
+            ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+            cache[key] = ws
+        return ws
 
     def lbs_workspace(self, N):
-        n = lib().rohm_smplx_lbs_workspace_bytes(self.handle, N)
-        if self._lbs_ws is None or self._lbs_ws.numel() < n:
-            self._lbs_ws = None
-            self._lbs_ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        return self._lbs_ws
+        return self._per_stream(self._lbs_ws, lib().rohm_smplx_lbs_workspace_bytes(self.handle, N))
 
     def workspace(self, B, T):
-        n = lib().rohm_guidance_workspace_bytes(B, T)
-        if self._ws is None or self._ws.numel() < n:
-            self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._per_stream(self._ws, lib().rohm_guidance_workspace_bytes(B, T))
 
     def __del__(self):
         try:

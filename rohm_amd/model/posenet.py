@@ -94,7 +94,7 @@ class _NativePoseNet:
             nbytes = lib().rohm_posenet_workspace_bytes(self.handle, B, T)
             if nbytes == 0:
                 raise _lib.RohmHipError('rohm_posenet_workspace_bytes returned 0 (bad shape)')
-            for k in [k for k in self._ws if k[2] == key[2]]:      # one live shape per stream
+            for k in [k for k in list(self._ws) if k[2] == key[2]]:      # one live shape per stream
                 del self._ws[k]
             ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             self._ws[key] = ws

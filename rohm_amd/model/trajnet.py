@@ -112,7 +112,7 @@ class _NativeTrajNet:
             n = lib().rohm_trajnet_workspace_bytes(self.handle, B, T)
             if n == 0:
                 raise _lib.RohmHipError(f'TrajNet: unsupported shape B={B}, T={T} (T must be a multiple of 16)')
-            for k in [k for k in self._ws if k[2] == key[2]]:
+            for k in [k for k in list(self._ws) if k[2] == key[2]]:
                 del self._ws[k]
             ws = torch.empty(n, dtype=torch.uint8, device=self.device)
             self._ws[key] = ws
