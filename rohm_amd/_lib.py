@@ -263,6 +263,18 @@ SIGNATURES = {
     'rohm_rig_ba_update': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_double] * 3 + [C.c_void_p] * 3),
 }
 
+# include/provisional/: headers written to the standard of HEADERS whose declarations have no case in the contract registries of
+# tests/ yet (tests/header_cases.py); their own tests hold them to the contracts until they move up.  lib() applies these rows after
+# SIGNATURES under the same strict rule.
+PROVISIONAL_HEADERS = ('rohm_sync.h',)
+
+PROVISIONAL_SIGNATURES = {
+    # include/provisional/rohm_sync.h
+    'rohm_sync_ws_bytes': (C.c_longlong, [C.c_int, C.c_longlong]),
+    'rohm_sync_pair_sweep': (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_double] * 3 + [C.c_void_p] * 3),
+    'rohm_sync_resample': (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p] * 2),
+}
+
 
 def lib():
     """Load (once) and return the ctypes library; raises if it has not been built."""
@@ -276,7 +288,7 @@ def lib():
         # the shipped library must export every declared symbol; an experiment library selected through ROHM_HIP_LIB (same-box A/B
         # runs against an older tree, scripts/build_variant.py) may lack the newest ones -- they then fail where they are used
         strict = not os.environ.get('ROHM_HIP_LIB')
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(PROVISIONAL_SIGNATURES.items()):
             if not strict and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)

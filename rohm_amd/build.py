@@ -24,7 +24,7 @@ def sources():
 
 def _deps():
     return sources() + glob.glob(os.path.join(CSRC, '*.h')) + \
-        glob.glob(os.path.join(HERE, '..', 'include', '*.h'))
+        glob.glob(os.path.join(HERE, '..', 'include', '*.h')) + glob.glob(os.path.join(HERE, '..', 'include', 'provisional', '*.h'))
 
 
 def is_stale():

@@ -4,7 +4,7 @@
 // spanning tree, the LM schedule and the Cholesky solve of the 6 V camera unknowns are host logic); tests/rig_ref.py restates them
 // in numpy; include/rohm_rig.h states the rule in full.  There is no counterpart in the reference.
 //
-// The camera row is camera_math.h's, shared with multiview.hip and fit_views.hip; the rotation update is fit_math.h's rodrigues64.
+// The camera row is camera_math.h's, shared with multiview.hip and fit_views.hip; epipolar_math.h holds what sync.hip shares; the rotation update is fit_math.h's rodrigues64.
 // All arithmetic is float64 on the float32 keypoints.  No atomics: the scores are integer counts, and every float64 sum has one owner
 // that adds in a fixed order, or is a fixed butterfly: the same input gives the same bits.
 //
@@ -22,6 +22,7 @@
 // closing launch mirrors.
 #include "common.h"
 #include "camera_math.h"
+#include "epipolar_math.h"
 #include "fit_math.h"
 #include "../../include/rohm_rig.h"
 
@@ -29,8 +30,6 @@
 
 namespace rohm {
 
-constexpr int kRigMaxViews = 16;
-constexpr long long kRigMaxPoints = 1ll << 29;
 constexpr long long kRigMaxHyp = 1ll << 27;
 constexpr int kRigThreads = 256;
 constexpr int kRigHypLanes = 16;                     // lanes that share an eigenproblem; hypotheses side by side in the scoring
@@ -48,7 +47,7 @@ constexpr int kBaSlots = 4;                          // strips of S per thread: 
 constexpr int kBaCam = 29;                           // per view: U (21), g_c (6), E, the count
 constexpr double kBaDiagEps = 1e-9;
 
-// ---- the undistorted coordinates of every view, once ----
+// ---- the undistorted coordinates of every view, once (sync.hip launches it too, through epipolar_math.h's rig_undistort) ----
 __global__ __launch_bounds__(256) void rig_undistort_kernel(const float* __restrict__ kp, const double* __restrict__ cams, long long P,
                                                             long long total, double conf_min, double* __restrict__ und) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -62,16 +61,6 @@ __global__ __launch_bounds__(256) void rig_undistort_kernel(const float* __restr
     }
     und[i * 2] = a;
     und[i * 2 + 1] = b;
-}
-
-__device__ __forceinline__ bool rig_pair_ok(int v1, int v2, int V) { return v1 >= 0 && v1 < V && v2 >= 0 && v2 < V && v1 != v2; }
-
-// x2^T E x1 times the pixel scale and the squared gradient norm of rule 4
-__device__ __forceinline__ void rig_sampson(const double* E, double a1, double b1, double a2, double b2, double scale, double& ns, double& den) {
-    const double l0 = E[0] * a1 + E[1] * b1 + E[2], l1 = E[3] * a1 + E[4] * b1 + E[5], l2 = E[6] * a1 + E[7] * b1 + E[8];
-    const double m0 = E[0] * a2 + E[3] * b2 + E[6], m1 = E[1] * a2 + E[4] * b2 + E[7];
-    ns = (a2 * l0 + b2 * l1 + l2) * scale;
-    den = l0 * l0 + l1 * l1 + m0 * m0 + m1 * m1;
 }
 
 // the sum of v over the 16 groups of lanes that share a hypothesis lane (floor.hip's floor_group_sum); every thread gets it
@@ -669,7 +658,7 @@ static BaPlan ba_plan(int V, long long P) {
     return b;
 }
 
-static int rig_undistort(const float* keypoints, const double* cams, int V, long long P, double conf_min, void* ws, hipStream_t stream) {
+int rig_undistort(const float* keypoints, const double* cams, int V, long long P, double conf_min, void* ws, hipStream_t stream) {
     const long long total = (long long)V * P;
     hipLaunchKernelGGL(rig_undistort_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, keypoints, cams, P, total, conf_min,
                        (double*)ws);

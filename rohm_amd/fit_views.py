@@ -24,8 +24,8 @@ for frames where that chain yields nothing): two candidates, a body that stands 
 and one that turns its back, each with its translation solved in closed form by the kernel; both run, as 2 N problems in one
 launch, and the smaller final energy wins.
 
-Limits.  One person; synchronised, calibrated views; 1 to 16 of them.  The shape is GIVEN (`betas`, default the mean shape), not
-fitted: with one view scale and depth are not separable -- a larger body further away gives the same pixels -- so a wrong shape
+Limits.  One person; synchronised (`python -m rohm_amd.sync`), calibrated views; 1 to 16 of them.  The shape is GIVEN (`betas`,
+default the mean shape), not fitted: with one view scale and depth are not separable -- a larger body further away gives the same pixels -- so a wrong shape
 turns into a wrong distance.  There is no learned pose prior.  With several views this is a refinement with millimetre accuracy
 on the synthetic body (measured with the restatement at 2 px of noise: 7 mm in the mean and 20 mm in the worst joint with two
 views, 4 mm and 13 mm with four); with ONE view the pixels are met (0.5 px) but the depth along the viewing ray is held by the

@@ -19,8 +19,9 @@ result: NaN joints with confidence 0, which `rohm_amd.fit` treats as missing.
 
 `tau_px`, `conf_min`, `min_angle_deg` and `min_views` are stated parameters: chosen, not fitted to recordings.
 
-Limits: synchronised cameras (per-view time offsets are not estimated); one person (detections are not associated across
-people); a calibrated rig (`python -m rohm_amd.rig` calibrates one from the keypoints themselves); 2 to 16 views.  With
+Limits: synchronised cameras (per-view time offsets are not estimated here: `python -m rohm_amd.sync` first); one person
+(detections are not associated across people); a calibrated rig (`python -m rohm_amd.rig` calibrates one from the keypoints
+themselves); 2 to 16 views.  With
 exactly three observed views and one mis-detection the counts tie at 2 and only the cost decides, which kept a few outliers
 per hundred such points in the prototype of this rule: use `--min_views 3` where four or more cameras see the person."""
 from __future__ import annotations

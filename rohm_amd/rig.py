@@ -24,8 +24,9 @@ neighbour is `--baseline_m`; `none`: that distance is 1.
 
 `tau_px`, `sigma_px`, `hypotheses` and `min_inliers` are stated parameters: chosen on synthetic data, not fitted to recordings.
 
-Limits: known intrinsics (and distortion); synchronised views (per-view time offsets are not estimated); one person; a static
-rig; a person who moves through the volume -- a person who stands still gives a near-planar, near-degenerate cloud, which the
+Limits: known intrinsics (and distortion); synchronised views (per-view time offsets are not estimated here: `python -m
+rohm_amd.sync` first); one person; a static rig; a person who moves through the volume -- a person who stands still gives a
+near-planar, near-degenerate cloud, which the
 report shows as a low inlier share."""
 from __future__ import annotations
 
