@@ -358,6 +358,16 @@ def hip_rows(x, name, shape, kernels):
     return x
 
 
+UP_AXIS = {'z': 2, 'y': 1}
+
+
+def up_index(up_axis):
+    """'z' or 'y' -> the coordinate index the floor and quality kernels take as up_axis."""
+    if up_axis not in UP_AXIS:
+        raise ValueError(f"up_axis must be 'z' or 'y', got {up_axis!r}")
+    return UP_AXIS[up_axis]
+
+
 def npz_dict(source):
     """The arrays of an .npz path (no pickles), or a copy of a mapping."""
     if isinstance(source, (str, os.PathLike)):

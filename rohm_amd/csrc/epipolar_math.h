@@ -1,14 +1,12 @@
-// What rig.hip and sync.hip share of the epipolar geometry of a pair of views: the limits, the once-per-call undistortion of every
+// What rig.hip and sync.hip share of the epipolar geometry of a pair of views: the limits (views_args.h's), the once-per-call undistortion of every
 // view's points into the workspace (rule 1 of rohm_multiview.h; the kernel lives in rig.hip, one copy in the library), the pair
 // test and the Sampson terms of rule 4 of rohm_rig.h.
 #pragma once
 #include "common.h"
 #include "camera_math.h"
+#include "views_args.h"
 
 namespace rohm {
-
-constexpr int kRigMaxViews = 16;
-constexpr long long kRigMaxPoints = 1ll << 29;
 
 // und [V,P,2] float64 into ws: (a, b) of every detection, NaN where it is unobserved or its undistortion is not finite.  One launch.
 int rig_undistort(const float* keypoints, const double* cams, int V, long long P, double conf_min, void* ws, hipStream_t stream);

@@ -18,6 +18,7 @@
 // terms per iteration) and to the factorisation (69 steps, two barriers each; the triangular solves take one barrier per
 // step).
 #include "fit_math.h"
+#include "reduce.h"
 
 #include <limits.h>
 
@@ -378,22 +379,14 @@ __global__ __launch_bounds__(kFitMomThreads) void fit_shape_moments_kernel(const
     }
 }
 
-// out[k] = sum over the frames of per_frame[., k]: one workgroup per k, thread t takes the frames t, t + 256, ..., a xor-butterfly
-// per wave, then the 4 wave partials in wave order
+// out[k] = sum over the frames of per_frame[., k]: one workgroup per k, thread t takes the frames t, t + 256, ... in ascending order,
+// then reduce.h's block_reduce of one value (a xor-butterfly per wave, the 4 wave partials in wave order)
 __global__ __launch_bounds__(kFitTotThreads) void fit_shape_total_kernel(const double* __restrict__ per_frame, int N, double* __restrict__ out) {
-    __shared__ double sh[kFitTotThreads / 64];
+    __shared__ double sh[kFitTotThreads / 64][1];
     const int tid = threadIdx.x, k = blockIdx.x;
-    double v = 0.0;
-    for (int i = tid; i < N; i += kFitTotThreads) v += per_frame[(size_t)i * kFitMom + k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((tid & 63) == 0) sh[tid >> 6] = v;
-    __syncthreads();
-    if (tid == 0) {
-        double t = sh[0];
-        for (int w = 1; w < kFitTotThreads / 64; ++w) t += sh[w];
-        out[k] = t;
-    }
+    double v[1] = {0.0};
+    for (int i = tid; i < N; i += kFitTotThreads) v[0] += per_frame[(size_t)i * kFitMom + k];
+    block_reduce<kFitTotThreads, 1>(v, sh, out + k, SumOfK());
 }
 
 }  // namespace rohm

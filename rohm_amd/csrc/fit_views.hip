@@ -17,11 +17,12 @@
 // CU's 160 KiB as in fit.hip.  The undistortion runs once, in the prologue, (view, joint) entries across the threads.
 #include "camera_math.h"
 #include "fit_math.h"
+#include "views_args.h"
 #include "../../include/rohm_fit_views.h"
 
 namespace rohm {
 
-constexpr int kFvMaxViews = 16;                      // (of a camera row's 24 values the iteration keeps kCamPinhole = 14: R, t, fx, fy)
+constexpr int kFvMaxViews = kViewsMax;               // (of a camera row's 24 values the iteration keeps kCamPinhole = 14: R, t, fx, fy)
 constexpr int kFvReport = 8;
 constexpr double kFvSingular = 1e-12;                // the start translation's system is singular when det <= this * trace^3
 

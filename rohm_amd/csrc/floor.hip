@@ -20,6 +20,7 @@
 // lanes along the hypotheses (128 workgroups) 4.9 ms, 8 lanes 3.7 ms, 8 lanes with the next tile's loads in flight 2.1 ms
 // -- with one wave per SIMD nothing else hides the staging's latency.
 #include "common.h"
+#include "reduce.h"
 
 #include <limits.h>
 
@@ -135,18 +136,6 @@ __device__ __forceinline__ void floor_count(const float* __restrict__ src, int n
     }
 }
 
-// the sum of v over the 16 groups of lanes that share a hypothesis lane; every thread gets it
-__device__ __forceinline__ int floor_group_sum(int v, int* shc, int tid) {
-#pragma unroll
-    for (int o = kFHypLanes; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-    const int l = tid % kFHypLanes;
-    if ((tid & 63) < kFHypLanes) shc[(tid >> 6) * kFHypLanes + l] = v;
-    __syncthreads();
-    const int r = shc[l] + shc[kFHypLanes + l] + shc[2 * kFHypLanes + l] + shc[3 * kFHypLanes + l];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(kFThreads) void floor_hypotheses_kernel(const FloorHypArgs a) {
     __shared__ double sh[kFTile * 3];
     __shared__ int shc[4 * kFHypLanes];
@@ -186,8 +175,8 @@ __global__ __launch_bounds__(kFThreads) void floor_hypotheses_kernel(const Floor
     floor_count<false>(a.joints, a.NJ, pl, a.under_tol, sh, tid, pos, neg);
 #pragma unroll
     for (int q = 0; q < kFPlanesPerLane; ++q) {
-        pos[q] = floor_group_sum(pos[q], shc, tid);
-        neg[q] = floor_group_sum(neg[q], shc, tid);
+        pos[q] = group_sum<kFHypLanes>(pos[q], shc, tid);
+        neg[q] = group_sum<kFHypLanes>(neg[q], shc, tid);
         if (neg[q] > pos[q]) {                       // the body is on the other side: turn the plane over; a tie keeps it
 #pragma unroll
             for (int k = 0; k < 4; ++k) pl[q][k] = -pl[q][k];
@@ -197,7 +186,7 @@ __global__ __launch_bounds__(kFThreads) void floor_hypotheses_kernel(const Floor
     floor_count<true>(a.points, a.P, pl, a.tau, sh, tid, sup, unused);
 #pragma unroll
     for (int q = 0; q < kFPlanesPerLane; ++q) {
-        sup[q] = floor_group_sum(sup[q], shc, tid);
+        sup[q] = group_sum<kFHypLanes>(sup[q], shc, tid);
         if (tid < kFHypLanes && hyp[q] >= 0) {
             const size_t h = (size_t)hyp[q];
 #pragma unroll
@@ -206,33 +195,6 @@ __global__ __launch_bounds__(kFThreads) void floor_hypotheses_kernel(const Floor
             a.scores[h * 3 + 1] = live[q] ? (long long)sup[q] : 0;
             a.scores[h * 3 + 2] = live[q] ? (long long)neg[q] : 0;
         }
-    }
-}
-
-struct BestScore {
-    long long s;
-    int h;
-};
-
-// the larger score; the lower index on ties
-__device__ __forceinline__ BestScore better_of(BestScore a, BestScore b) { return (b.s > a.s || (b.s == a.s && b.h < a.h)) ? b : a; }
-
-__global__ __launch_bounds__(kFBestThreads) void floor_best_kernel(const long long* __restrict__ scores, int K, int* __restrict__ best) {
-    __shared__ long long sh_s[kFBestThreads / 64];
-    __shared__ int sh_h[kFBestThreads / 64];
-    const int tid = threadIdx.x;
-    BestScore b = {LLONG_MIN, INT_MAX};
-    for (int h = tid; h < K; h += kFBestThreads) b = better_of(b, BestScore{scores[(size_t)h * 3], h});
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) b = better_of(b, BestScore{__shfl_xor(b.s, o, 64), __shfl_xor(b.h, o, 64)});
-    if ((tid & 63) == 0) {
-        sh_s[tid >> 6] = b.s;
-        sh_h[tid >> 6] = b.h;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < kFBestThreads / 64; ++w) b = better_of(b, BestScore{sh_s[w], sh_h[w]});
-        best[0] = b.s == LLONG_MIN ? -1 : b.h;       // a degenerate triple scores LLONG_MIN: all of them degenerate gives -1
     }
 }
 
@@ -246,8 +208,8 @@ struct FloorMomArgs {
     double* out;                  // [11]
 };
 
-// One workgroup, as the totals of rohm_track_quality: thread t takes the points t, t + 1024, ..., a xor-butterfly per wave, then
-// the 16 wave partials in wave order.  Tens of thousands of contacts are a few dozen points per thread.
+// One workgroup: thread t takes the points t, t + 1024, ... in ascending order, then reduce.h's block_reduce (a xor-butterfly per
+// wave, the 16 wave partials in wave order).  Tens of thousands of contacts are a few dozen points per thread.
 __global__ __launch_bounds__(kFMomThreads) void floor_moments_kernel(const FloorMomArgs a) {
     __shared__ double shm[kFMomThreads / 64][kFMoments];
     const int tid = threadIdx.x;
@@ -268,19 +230,7 @@ __global__ __launch_bounds__(kFMomThreads) void floor_moments_kernel(const Floor
             m[10] += r * r;
         }
     }
-#pragma unroll
-    for (int k = 0; k < kFMoments; ++k) {
-        double v = m[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if ((tid & 63) == 0) shm[tid >> 6][k] = v;
-    }
-    __syncthreads();
-    if (tid < kFMoments) {
-        double v = shm[0][tid];
-        for (int w = 1; w < kFMomThreads / 64; ++w) v += shm[w][tid];
-        a.out[tid] = v;
-    }
+    block_reduce<kFMomThreads, kFMoments>(m, shm, a.out, SumOfK());
 }
 
 }  // namespace rohm
@@ -337,7 +287,8 @@ extern "C" int rohm_floor_hypotheses(const float* points, int P, const float* jo
                    (hipStream_t)stream);
     hipLaunchKernelGGL(floor_hypotheses_kernel, dim3(blocks), dim3(kFThreads), 0, (hipStream_t)stream, a);
     ROHM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(floor_best_kernel, dim3(1), dim3(kFBestThreads), 0, (hipStream_t)stream, scores, K, best);
+    // a degenerate triple scores LLONG_MIN, below any live score (support minus under-count may be negative): all of them degenerate gives -1
+    hipLaunchKernelGGL((best_score_kernel<kFBestThreads, 3, LLONG_MIN + 1>), dim3(1), dim3(kFBestThreads), 0, (hipStream_t)stream, scores, K, best);
     ROHM_LAUNCH_CHECK();
     return ROHM_OK;
 }

@@ -8,24 +8,13 @@
 // Comparisons are done in float32 exactly as numpy does them on the float32 joint arrays (velocity and height
 // thresholds of the skating test, the -0.05 m penetration test); sums are accumulated in float64.
 #include "common.h"
+#include "reduce.h"
 
 namespace rohm {
 
 constexpr int kMJ = 22;
 constexpr int kNMetric = 10;     // layout documented in include/rohm_hip.h
 __constant__ int kMFoot[4] = {7, 10, 8, 11};      // eval_amass_full.py:103
-
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-    for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-        if (tid < o) sh[tid] += sh[tid + o];
-        __syncthreads();
-    }
-    return sh[0];
-}
 
 __device__ __forceinline__ bool skating_at(const float* __restrict__ j, int t, float min_h) {
     // both joints of both feet faster than 0.10 m/s horizontally and lower than 0.15 m (ankle) / 0.10 m (toe)
@@ -49,7 +38,6 @@ __global__ __launch_bounds__(256) void amass_metrics_kernel(const float* __restr
                                                             unsigned occ_joint_mask, int occ_start, int occ_end,
                                                             double* __restrict__ out, int T) {
     __shared__ double sh[256];
-    __shared__ float sh_min;
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* c = jc + (size_t)b * T * kMJ * 3;
     const float* r = jr + (size_t)b * T * kMJ * 3;
@@ -57,15 +45,7 @@ __global__ __launch_bounds__(256) void amass_metrics_kernel(const float* __restr
     float mn = INFINITY;
     for (int i = tid; i < T * kMJ; i += blockDim.x) mn = fminf(mn, c[(size_t)i * 3 + 2]);
     __shared__ float shf[256];
-    shf[tid] = mn;
-    __syncthreads();
-    for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-        if (tid < o) shf[tid] = fminf(shf[tid], shf[tid + o]);
-        __syncthreads();
-    }
-    if (tid == 0) sh_min = shf[0];
-    __syncthreads();
-    const float min_h = sh_min;
+    const float min_h = block_tree_reduce(mn, shf, MinOp());
 
     double s_all = 0, s_occ = 0, n_occ = 0, n_contact = 0, n_sk_gt = 0, n_sk_rec = 0, s_acc = 0, n_pene = 0, s_pene = 0;
     for (int i = tid; i < T * kMJ; i += blockDim.x) {
@@ -106,7 +86,7 @@ __global__ __launch_bounds__(256) void amass_metrics_kernel(const float* __restr
     }
     double vals[kNMetric] = {s_all, s_occ, n_occ, n_contact, n_sk_gt, n_sk_rec, s_acc, n_pene, s_pene, (double)min_h};
     for (int k = 0; k < kNMetric - 1; ++k) {
-        const double v = block_sum(vals[k], sh);
+        const double v = block_tree_reduce(vals[k], sh, SumOp());
         if (tid == 0) out[(size_t)b * kNMetric + k] = v;
     }
     if (tid == 0) out[(size_t)b * kNMetric + kNMetric - 1] = (double)min_h;

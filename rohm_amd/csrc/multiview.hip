@@ -18,19 +18,19 @@
 // W, so both widths give the same bits.  One thread per point with 16 rays in registers spills; a group per point does not.
 #include "common.h"
 #include "camera_math.h"
+#include "reduce.h"
+#include "views_args.h"
 #include "../../include/rohm_multiview.h"
 
 #include <limits.h>
 
 namespace rohm {
 
-constexpr int kMvMaxViews = 16;
-constexpr int kMvMaxPairs = kMvMaxViews * (kMvMaxViews - 1) / 2;
+constexpr int kMvMaxPairs = kViewsMax * (kViewsMax - 1) / 2;
 constexpr int kMvThreads = 256;
 constexpr int kMvSmallViews = 6;                     // up to this many views the pairs (15) fit a group of 16 lanes
 constexpr int kMvRay = 9;                            // o (3), d (3), a, b, c
 constexpr int kMvMaxRefine = 64;
-constexpr long long kMvMaxPoints = 1ll << 29;
 
 struct MvArgs {
     const float* kp;
@@ -60,19 +60,12 @@ __device__ __forceinline__ void mv_ray_terms(double w, const double* o, const do
     b[2] = w * (o[2] - d[2] * od);
 }
 
-// the sum over lanes 0..15 (a fixed xor-butterfly), in every one of them
-__device__ __forceinline__ double mv_sum16(double v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // W lanes per point: 64 (a wave; any V), or 16 when the pairs fit 16 lanes (V <= 6: four points per wave).  Everything a group of W
 // lanes decides is uniform in the group, and every shuffle stays inside it, so the groups of a wave never read one another.
 template <int W>
 __global__ __launch_bounds__(kMvThreads) void mv_triangulate_kernel(const MvArgs g) {
     constexpr int kPoints = kMvThreads / W;          // points per workgroup
-    constexpr int kViews = W == 64 ? kMvMaxViews : kMvSmallViews;
+    constexpr int kViews = W == 64 ? kViewsMax : kMvSmallViews;
     __shared__ double rays[kPoints][kViews][kMvRay];
     const int lane = threadIdx.x % W, wave = threadIdx.x / W;      // the lane in its group, the group in its workgroup
     const long long P = (long long)g.N * g.J;
@@ -175,15 +168,9 @@ __global__ __launch_bounds__(kMvThreads) void mv_triangulate_kernel(const MvArgs
             best_mask = mask;
         }
     }
-    int n_max = best_n;
-#pragma unroll
-    for (int s = W / 2; s > 0; s >>= 1) n_max = max(n_max, __shfl_xor(n_max, s, 64));
-    double c_min = best_n == n_max ? best_cost : (double)INFINITY;
-#pragma unroll
-    for (int s = W / 2; s > 0; s >>= 1) c_min = fmin(c_min, __shfl_xor(c_min, s, 64));
-    int q_min = (best_n == n_max && best_cost == c_min) ? best_q : INT_MAX;
-#pragma unroll
-    for (int s = W / 2; s > 0; s >>= 1) q_min = min(q_min, __shfl_xor(q_min, s, 64));
+    const int n_max = lanes_reduce<W>(best_n, MaxOp());
+    const double c_min = lanes_reduce<W>(best_n == n_max ? best_cost : (double)INFINITY, MinOp());
+    const int q_min = lanes_reduce<W>((best_n == n_max && best_cost == c_min) ? best_q : INT_MAX, MinOp());
 
     // ---- rule 3
     if (n_max < 2 || n_max < g.min_views || q_min == INT_MAX) {
@@ -211,29 +198,29 @@ __global__ __launch_bounds__(kMvThreads) void mv_triangulate_kernel(const MvArgs
         double At[6], bt[3];
         mv_ray_terms(w, o, d, At, bt);
 #pragma unroll
-        for (int k = 0; k < 6; ++k) A[k] = mv_sum16(inl ? At[k] : 0.0);
+        for (int k = 0; k < 6; ++k) A[k] = lanes_sum<16>(inl ? At[k] : 0.0);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) t3[k] = mv_sum16(inl ? bt[k] : 0.0);
+        for (int k = 0; k < 3; ++k) t3[k] = lanes_sum<16>(inl ? bt[k] : 0.0);
         cam_solve3(A, t3, X0);
     }
-    const double sum_c = mv_sum16(w);
+    const double sum_c = lanes_sum<16>(w);
 #pragma unroll
     for (int k = 0; k < 3; ++k) X[k] = X0[k];
     double E0 = 0.0, E = 0.0;
     for (int it = 0; it <= g.refine; ++it) {
         double r[2], j0[3], j1[3];
         const double e2 = cam_residual<true>(cam, X, a, b, r, j0, j1);
-        E = mv_sum16(inl ? w * e2 : 0.0);
+        E = lanes_sum<16>(inl ? w * e2 : 0.0);
         if (it == 0) E0 = E;
         if (it == g.refine) break;
-        A[0] = mv_sum16(inl ? w * (j0[0] * j0[0] + j1[0] * j1[0]) : 0.0);
-        A[1] = mv_sum16(inl ? w * (j0[0] * j0[1] + j1[0] * j1[1]) : 0.0);
-        A[2] = mv_sum16(inl ? w * (j0[0] * j0[2] + j1[0] * j1[2]) : 0.0);
-        A[3] = mv_sum16(inl ? w * (j0[1] * j0[1] + j1[1] * j1[1]) : 0.0);
-        A[4] = mv_sum16(inl ? w * (j0[1] * j0[2] + j1[1] * j1[2]) : 0.0);
-        A[5] = mv_sum16(inl ? w * (j0[2] * j0[2] + j1[2] * j1[2]) : 0.0);
+        A[0] = lanes_sum<16>(inl ? w * (j0[0] * j0[0] + j1[0] * j1[0]) : 0.0);
+        A[1] = lanes_sum<16>(inl ? w * (j0[0] * j0[1] + j1[0] * j1[1]) : 0.0);
+        A[2] = lanes_sum<16>(inl ? w * (j0[0] * j0[2] + j1[0] * j1[2]) : 0.0);
+        A[3] = lanes_sum<16>(inl ? w * (j0[1] * j0[1] + j1[1] * j1[1]) : 0.0);
+        A[4] = lanes_sum<16>(inl ? w * (j0[1] * j0[2] + j1[1] * j1[2]) : 0.0);
+        A[5] = lanes_sum<16>(inl ? w * (j0[2] * j0[2] + j1[2] * j1[2]) : 0.0);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) t3[k] = mv_sum16(inl ? w * (j0[k] * r[0] + j1[k] * r[1]) : 0.0);
+        for (int k = 0; k < 3; ++k) t3[k] = lanes_sum<16>(inl ? w * (j0[k] * r[0] + j1[k] * r[1]) : 0.0);
         double dX[3];
         cam_solve3(A, t3, dX);
 #pragma unroll
@@ -248,12 +235,12 @@ __global__ __launch_bounds__(kMvThreads) void mv_triangulate_kernel(const MvArgs
     {
         double r[2], j0[3], j1[3];
         cam_residual<true>(cam, X, a, b, r, j0, j1);
-        A[0] = mv_sum16(inl ? j0[0] * j0[0] + j1[0] * j1[0] : 0.0);
-        A[1] = mv_sum16(inl ? j0[0] * j0[1] + j1[0] * j1[1] : 0.0);
-        A[2] = mv_sum16(inl ? j0[0] * j0[2] + j1[0] * j1[2] : 0.0);
-        A[3] = mv_sum16(inl ? j0[1] * j0[1] + j1[1] * j1[1] : 0.0);
-        A[4] = mv_sum16(inl ? j0[1] * j0[2] + j1[1] * j1[2] : 0.0);
-        A[5] = mv_sum16(inl ? j0[2] * j0[2] + j1[2] * j1[2] : 0.0);
+        A[0] = lanes_sum<16>(inl ? j0[0] * j0[0] + j1[0] * j1[0] : 0.0);
+        A[1] = lanes_sum<16>(inl ? j0[0] * j0[1] + j1[0] * j1[1] : 0.0);
+        A[2] = lanes_sum<16>(inl ? j0[0] * j0[2] + j1[0] * j1[2] : 0.0);
+        A[3] = lanes_sum<16>(inl ? j0[1] * j0[1] + j1[1] * j1[1] : 0.0);
+        A[4] = lanes_sum<16>(inl ? j0[1] * j0[2] + j1[1] * j1[2] : 0.0);
+        A[5] = lanes_sum<16>(inl ? j0[2] * j0[2] + j1[2] * j1[2] : 0.0);
         t3[0] = t3[1] = t3[2] = 0.0;
         double unused[3];
         const CamSolve3 q = cam_solve3(A, t3, unused);
@@ -307,13 +294,9 @@ __global__ __launch_bounds__(256) void mv_residuals_kernel(const double* __restr
     resid[i] = out;
 }
 
-static int mv_check_shape(const char* who, int V, int N, int J, double conf_min) {
-    ROHM_ARG_CHECK(V >= 2 && V <= kMvMaxViews, "%s: V must be in [2, %d], got %d", who, kMvMaxViews, V);
-    ROHM_ARG_CHECK(N >= 0, "%s: N must be >= 0, got %d", who, N);
-    ROHM_ARG_CHECK(J >= 1, "%s: J must be >= 1, got %d", who, J);
-    ROHM_ARG_CHECK((long long)N * J <= kMvMaxPoints, "%s: N * J must not exceed %lld, got %lld", who, kMvMaxPoints, (long long)N * J);
-    ROHM_ARG_CHECK(isfinite(conf_min), "%s: conf_min must be finite", who);
-    return ROHM_OK;
+static int mv_check(const char* who, int V, int N, int J, double conf_min) {
+    if (int rc = views_check_shape(who, V, 2, N, 0, J)) return rc;
+    return views_check_conf(who, conf_min);
 }
 
 }  // namespace rohm
@@ -321,7 +304,7 @@ static int mv_check_shape(const char* who, int V, int N, int J, double conf_min)
 using namespace rohm;
 
 extern "C" int rohm_mv_limits(int* max_views, int* max_pairs) {
-    if (max_views) *max_views = kMvMaxViews;
+    if (max_views) *max_views = kViewsMax;
     if (max_pairs) *max_pairs = kMvMaxPairs;
     return ROHM_OK;
 }
@@ -329,7 +312,7 @@ extern "C" int rohm_mv_limits(int* max_views, int* max_pairs) {
 extern "C" int rohm_mv_triangulate(const float* keypoints, const double* cams, const double* rigid, int V, int N, int J, double conf_min,
                                    double tau_px, double min_angle_rad, int min_views, int refine, double* joints, float* conf,
                                    double* report, uint32_t* inliers, float* keypoints_und, rohm_stream_t stream) {
-    if (int rc = mv_check_shape("mv_triangulate", V, N, J, conf_min)) return rc;
+    if (int rc = mv_check("mv_triangulate", V, N, J, conf_min)) return rc;
     ROHM_ARG_CHECK(isfinite(tau_px) && tau_px > 0.0, "mv_triangulate: tau_px must be finite and > 0, got %g", tau_px);
     ROHM_ARG_CHECK(min_angle_rad >= 0.0 && min_angle_rad <= 1.5707963267948966, "mv_triangulate: min_angle_rad must be in [0, pi / 2], got %g",
                    min_angle_rad);
@@ -362,7 +345,7 @@ extern "C" int rohm_mv_triangulate(const float* keypoints, const double* cams, c
 
 extern "C" int rohm_mv_residuals(const double* joints_world, const float* keypoints, const double* cams, int V, int N, int J,
                                  double conf_min, double* resid, rohm_stream_t stream) {
-    if (int rc = mv_check_shape("mv_residuals", V, N, J, conf_min)) return rc;
+    if (int rc = mv_check("mv_residuals", V, N, J, conf_min)) return rc;
     if (N == 0) return ROHM_OK;
     ROHM_ARG_CHECK(joints_world, "mv_residuals: joints_world is null");
     ROHM_ARG_CHECK(keypoints, "mv_residuals: keypoints is null");

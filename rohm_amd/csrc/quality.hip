@@ -9,13 +9,14 @@
 // 256-thread workgroup takes 8 frames.  Flags and counts are ballots, sums and the maximum a xor-butterfly over the 32
 // lanes: a fixed order, every lane ends with the same bits.  All arithmetic is float64 on the float32 inputs.  A second
 // launch of one workgroup reduces the rows (and the toe heights, which the rows do not hold per toe) to totals [2,15] in a
-// fixed order: thread i takes frames i, i + 1024, ..., then the butterfly, then the 16 wave partials in wave order.  No
+// fixed order: thread i takes frames i, i + 1024, ..., then reduce.h's block_reduce, with max_nan in column 3.  No
 // atomics, no workspace: the same input gives the same bits.
 //
 // NaN rules (what the tests pin): a value is NaN exactly when a number it reads is.  The thresholds are written so that a
 // NaN reaches the result instead of failing a comparison silently: a joint with confidence above conf_min whose camera
 // coordinates are not finite makes columns 0 .. 2 NaN; a foot joint with a NaN speed or height makes skate NaN.
 #include "common.h"
+#include "reduce.h"
 
 namespace rohm {
 
@@ -26,6 +27,7 @@ constexpr int kQFramesPerBlock = 8;                  // 256 threads / 32 lanes
 constexpr unsigned kQFootBits = (1u << 7) | (1u << 8) | (1u << 10) | (1u << 11);      // ankles 7, 8 and toes 10, 11
 constexpr unsigned kQToeBits = (1u << 10) | (1u << 11);
 constexpr int kQTotThreads = 1024;
+constexpr int kQShfl = 32;                           // the width a half-wave hands to its shuffles
 
 struct QualityArgs {
     const float* joints;          // [N,22,3]
@@ -39,21 +41,6 @@ struct QualityArgs {
     double* rows;                 // [N,10]
     double* totals;               // [2,15]
 };
-
-__device__ __forceinline__ double half_sum(double v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
-    return v;
-}
-
-// the larger of two, a NaN wins
-__device__ __forceinline__ double max_nan(double a, double b) { return (a > b || a != a) ? a : b; }
-
-__device__ __forceinline__ double half_max(double v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v = max_nan(v, __shfl_xor(v, o, 32));
-    return v;
-}
 
 __device__ __forceinline__ unsigned half_ballot(bool p, int lane) {
     const unsigned long long b = __ballot(p);
@@ -103,9 +90,9 @@ __global__ __launch_bounds__(256) void track_quality_kernel(const QualityArgs a)
         }
     }
     const unsigned qual_bits = half_ballot(qual, lane), bad_bits = half_ballot(bad, lane);
-    s_cd = half_sum(s_cd);
-    s_c = half_sum(s_c);
-    d_max = half_max(d_max);
+    s_cd = lanes_sum<32, kQShfl>(s_cd);
+    s_c = lanes_sum<32, kQShfl>(s_c);
+    d_max = lanes_reduce<32, kQShfl>(d_max, MaxNanOp());
     double col0 = nan, col1 = nan, col2 = 0.0;
     if (a.has_cam) {
         const int n = __popc(qual_bits);
@@ -137,7 +124,7 @@ __global__ __launch_bounds__(256) void track_quality_kernel(const QualityArgs a)
         const double ax = (p2[0] - 2.0 * p1[0]) + p0[0], ay = (p2[1] - 2.0 * p1[1]) + p0[1], az = (p2[2] - 2.0 * p1[2]) + p0[2];
         acc = sqrt(ax * ax + ay * ay + az * az) * (a.fps * a.fps);
     }
-    acc = half_sum(acc);
+    acc = lanes_sum<32, kQShfl>(acc);
     const double col4 = has2 ? acc / (double)kQJ : nan;
 
     // ---- distance to the input track, split by its visibility mask: columns 6 .. 8 ----
@@ -150,7 +137,7 @@ __global__ __launch_bounds__(256) void track_quality_kernel(const QualityArgs a)
                      ez = p0[2] - (double)a.joints_ref[e + 2];
         dev = sqrt(ex * ex + ey * ey + ez * ez);
     }
-    const double s_vis = half_sum(vis ? dev : 0.0), s_occ = half_sum(occ ? dev : 0.0);
+    const double s_vis = lanes_sum<32, kQShfl>(vis ? dev : 0.0), s_occ = lanes_sum<32, kQShfl>(occ ? dev : 0.0);
     const double col6 = (a.joints_ref && n_vis > 0) ? s_vis / (double)n_vis : nan;
     const double col7 = (a.joints_ref && n_occ > 0) ? s_occ / (double)n_occ : nan;
 
@@ -164,16 +151,14 @@ __global__ __launch_bounds__(256) void track_quality_kernel(const QualityArgs a)
     }
 }
 
-// rows [N,10] (+ the toe heights) -> totals [2,15]; one workgroup
+// rows [N,10] (+ the toe heights) -> totals [2,15]; one workgroup.  acc holds the two groups' 15 values side by side, as totals does.
 __global__ __launch_bounds__(kQTotThreads) void track_quality_totals_kernel(const QualityArgs a) {
     __shared__ double sh[kQTotThreads / 64][2 * kQTot];
-    const int tid = threadIdx.x, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    double acc[2][kQTot];
+    double acc[2 * kQTot];
 #pragma unroll
-    for (int g = 0; g < 2; ++g)
-#pragma unroll
-        for (int k = 0; k < kQTot; ++k) acc[g][k] = (k == 3) ? -1.0 : 0.0;      // column 3 is a maximum of distances >= 0
+    for (int k = 0; k < 2 * kQTot; ++k) acc[k] = (k % kQTot == 3) ? -1.0 : 0.0;      // column 3 is a maximum of distances >= 0
     for (int t = tid; t < a.N; t += kQTotThreads) {
         const double* r = a.rows + (size_t)t * kQCols;
         double v[kQTot];
@@ -201,33 +186,15 @@ __global__ __launch_bounds__(kQTotThreads) void track_quality_totals_kernel(cons
 #pragma unroll
         for (int k = 0; k < kQTot; ++k) {
             if (k == 3) {
-                acc[0][k] = g1 ? acc[0][k] : max_nan(acc[0][k], v[k]);
-                acc[1][k] = g1 ? max_nan(acc[1][k], v[k]) : acc[1][k];
+                acc[k] = g1 ? acc[k] : max_nan(acc[k], v[k]);
+                acc[kQTot + k] = g1 ? max_nan(acc[kQTot + k], v[k]) : acc[kQTot + k];
             } else {
-                acc[0][k] += g1 ? 0.0 : v[k];
-                acc[1][k] += g1 ? v[k] : 0.0;
+                acc[k] += g1 ? 0.0 : v[k];
+                acc[kQTot + k] += g1 ? v[k] : 0.0;
             }
         }
     }
-#pragma unroll
-    for (int g = 0; g < 2; ++g)
-#pragma unroll
-        for (int k = 0; k < kQTot; ++k) {
-            double v = acc[g][k];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double w = __shfl_xor(v, o, 64);
-                v = (k == 3) ? max_nan(v, w) : v + w;
-            }
-            if ((tid & 63) == 0) sh[wave][g * kQTot + k] = v;
-        }
-    __syncthreads();
-    if (tid < 2 * kQTot) {
-        const int k = tid % kQTot;
-        double v = sh[0][tid];
-        for (int w = 1; w < kQTotThreads / 64; ++w) v = (k == 3) ? max_nan(v, sh[w][tid]) : v + sh[w][tid];
-        a.totals[tid] = v;
-    }
+    block_reduce<kQTotThreads, 2 * kQTot>(acc, sh, a.totals, [](int k, double x, double y) { return (k % kQTot == 3) ? max_nan(x, y) : x + y; });
     __syncthreads();
     if (tid < 2) {      // the maximum of a group without a reprojection residual is NaN
         if (a.totals[tid * kQTot + 2] == 0.0) a.totals[tid * kQTot + 3] = nan;
@@ -235,54 +202,31 @@ __global__ __launch_bounds__(kQTotThreads) void track_quality_totals_kernel(cons
 }
 
 // ---- floor clearance of a mesh: one workgroup per frame ----
-struct LowVertex {
-    double h;
-    int idx;
-};
-
-// the lower of two; the lower index on ties
-__device__ __forceinline__ LowVertex lower_of(LowVertex a, LowVertex b) {
-    return (b.h < a.h || (b.h == a.h && b.idx < a.idx)) ? b : a;
-}
-
 __global__ __launch_bounds__(256) void floor_clearance_kernel(const float* __restrict__ verts, int V, int up, double ground,
                                                               double below, double* __restrict__ out) {
     __shared__ double sh_h[4];
     __shared__ int sh_i[4];
     __shared__ int sh_n[4];
-    const int tid = threadIdx.x, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const float* v = verts + (size_t)blockIdx.x * V * 3 + (up == 2 ? 2 : 1);
-    LowVertex low = {__longlong_as_double(0x7ff0000000000000ll), 0x7fffffff};
+    Scored<double> low = {__longlong_as_double(0x7ff0000000000000ll), 0x7fffffff};      // the lowest vertex; the lower index on ties
     int n_below = 0, not_finite = 0;
     for (int i = tid; i < V; i += 256) {
         const double h = (double)v[(size_t)i * 3] - ground;
         not_finite |= !isfinite(h);
-        low = lower_of(low, LowVertex{h, i});
+        low = better_of<true>(low, Scored<double>{h, i});
         n_below += h < -below ? 1 : 0;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const LowVertex w = {__shfl_xor(low.h, o, 64), __shfl_xor(low.idx, o, 64)};
-        low = lower_of(low, w);
-        n_below += __shfl_xor(n_below, o, 64);
-    }
+    n_below = lanes_sum<64>(n_below);
     const int any_bad = __syncthreads_or(not_finite);
-    if ((tid & 63) == 0) {
-        sh_h[wave] = low.h;
-        sh_i[wave] = low.idx;
-        sh_n[wave] = n_below;
-    }
-    __syncthreads();
+    if ((tid & 63) == 0) sh_n[tid >> 6] = n_below;
+    low = block_arg_best<256, true>(low, sh_h, sh_i);      // its barrier publishes sh_n too
     if (tid == 0) {
-        int n = sh_n[0];
-        for (int w = 1; w < 4; ++w) {
-            low = lower_of(low, LowVertex{sh_h[w], sh_i[w]});
-            n += sh_n[w];
-        }
+        const int n = sh_n[0] + sh_n[1] + sh_n[2] + sh_n[3];
         const double nan = __longlong_as_double(0x7ff8000000000000ll);
         double* o = out + (size_t)blockIdx.x * 3;
-        o[0] = any_bad ? nan : low.h;
-        o[1] = any_bad ? -1.0 : (double)low.idx;
+        o[0] = any_bad ? nan : low.s;
+        o[1] = any_bad ? -1.0 : (double)low.h;
         o[2] = any_bad ? nan : (double)n;
     }
 }

@@ -24,6 +24,7 @@
 #include "camera_math.h"
 #include "epipolar_math.h"
 #include "fit_math.h"
+#include "reduce.h"
 #include "../../include/rohm_rig.h"
 
 #include <limits.h>
@@ -41,6 +42,7 @@ constexpr int kRigSweeps = 10;
 constexpr double kRigGapMin = 1e-12;
 constexpr int kRigMoments = 47;
 constexpr int kRigMomThreads = 256;
+constexpr int kRigPickThreads = 256;
 constexpr int kBaPts = 16;                           // points per tile, 16 lanes each
 constexpr int kBaMaxGroups = 256;
 constexpr int kBaSlots = 4;                          // strips of S per thread: 6 * 136 = 816 <= 4 * 256
@@ -61,18 +63,6 @@ __global__ __launch_bounds__(256) void rig_undistort_kernel(const float* __restr
     }
     und[i * 2] = a;
     und[i * 2 + 1] = b;
-}
-
-// the sum of v over the 16 groups of lanes that share a hypothesis lane (floor.hip's floor_group_sum); every thread gets it
-__device__ __forceinline__ int rig_group_sum(int v, int* shc, int tid) {
-#pragma unroll
-    for (int o = kRigHypLanes; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-    const int l = tid % kRigHypLanes;
-    if ((tid & 63) < kRigHypLanes) shc[(tid >> 6) * kRigHypLanes + l] = v;
-    __syncthreads();
-    const int r = shc[l] + shc[kRigHypLanes + l] + shc[2 * kRigHypLanes + l] + shc[3 * kRigHypLanes + l];
-    __syncthreads();
-    return r;
 }
 
 struct RigHypArgs {
@@ -235,10 +225,10 @@ __global__ __launch_bounds__(kRigThreads) void rig_hypotheses_kernel(const RigHy
             __syncthreads();
         }
     }
-    common = rig_group_sum(common, shc, tid);
+    common = group_sum<kRigHypLanes>(common, shc, tid);
 #pragma unroll
     for (int k = 0; k < kRigHypPerLane; ++k) {
-        const int n = rig_group_sum(inl[k], shc, tid);
+        const int n = group_sum<kRigHypLanes>(inl[k], shc, tid);
         const long long h = (long long)blockIdx.x * kRigHypPerBlock + k * kRigHypLanes + tid;
         if (tid < kRigHypLanes && h < g.K) {
             const bool live = E[k][0] == E[k][0];    // a degenerate hypothesis is all NaN
@@ -248,35 +238,7 @@ __global__ __launch_bounds__(kRigThreads) void rig_hypotheses_kernel(const RigHy
     }
 }
 
-struct RigBest {
-    long long s;
-    int h;
-};
-
-// the larger count; the lower index on ties
-__device__ __forceinline__ RigBest rig_better(RigBest a, RigBest b) { return (b.s > a.s || (b.s == a.s && b.h < a.h)) ? b : a; }
-
-__global__ __launch_bounds__(256) void rig_best_kernel(const long long* __restrict__ counts, int K, int* __restrict__ best) {
-    __shared__ long long sh_s[4];
-    __shared__ int sh_h[4];
-    const int tid = threadIdx.x;
-    const long long* c = counts + (size_t)blockIdx.x * (size_t)K * 2;
-    RigBest b = {-1, INT_MAX};
-    for (int h = tid; h < K; h += 256) b = rig_better(b, RigBest{c[(size_t)h * 2], h});
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) b = rig_better(b, RigBest{__shfl_xor(b.s, o, 64), __shfl_xor(b.h, o, 64)});
-    if ((tid & 63) == 0) {
-        sh_s[tid >> 6] = b.s;
-        sh_h[tid >> 6] = b.h;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w) b = rig_better(b, RigBest{sh_s[w], sh_h[w]});
-        best[blockIdx.x] = b.s < 0 ? -1 : b.h;       // a degenerate hypothesis counts -1: all of them degenerate gives -1
-    }
-}
-
-// ---- the sums of the inlier refit: one workgroup per pair ----
+// ---- the sums of the inlier refit: one workgroup per pair; thread t takes the points t, t + 256, ... in ascending order ----
 __global__ __launch_bounds__(kRigMomThreads) void rig_moments_kernel(const double* __restrict__ und, const double* __restrict__ cams,
                                                                      const int* __restrict__ pairs, const double* __restrict__ Es, int V,
                                                                      long long P, double tau2, double* __restrict__ out) {
@@ -313,19 +275,7 @@ __global__ __launch_bounds__(kRigMomThreads) void rig_moments_kernel(const doubl
                 for (int j = i; j < 9; ++j) m[k++] += row[i] * row[j];
         }
     }
-#pragma unroll
-    for (int k = 0; k < kRigMoments; ++k) {
-        double v = m[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if ((tid & 63) == 0) shm[tid >> 6][k] = v;
-    }
-    __syncthreads();
-    if (tid < kRigMoments) {
-        double v = shm[0][tid];
-        for (int w = 1; w < kRigMomThreads / 64; ++w) v += shm[w][tid];
-        out[(size_t)q * kRigMoments + tid] = v;
-    }
+    block_reduce<kRigMomThreads, kRigMoments>(m, shm, out + (size_t)q * kRigMoments, SumOfK());
 }
 
 // ---- bundle adjustment ----
@@ -342,13 +292,6 @@ struct BaArgs {
     double* points_new;
     double* cams_new;
 };
-
-// the sum over the 16 lanes of a point (a fixed xor-butterfly), in every one of them
-__device__ __forceinline__ double ba_sum16(double v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // What lane v holds of point p: the weight w = c rho' (0 when the lane adds nothing), the residual, the rows of J_X and J_c, its share
 // e of the energy and whether it is an observation; and, the same in all 16 lanes, whether the point is inside the problem, H_pp,d
@@ -424,14 +367,14 @@ __device__ __forceinline__ void ba_lane(const BaArgs& g, long long p, int lane, 
     }
     o.seen = (unsigned)(__ballot(adds) >> ((threadIdx.x & 63) - lane)) & 0xffffu;
     const double w = o.w;
-    o.Hd[0] = ba_sum16(w * (o.jx[0][0] * o.jx[0][0] + o.jx[1][0] * o.jx[1][0]));
-    o.Hd[1] = ba_sum16(w * (o.jx[0][0] * o.jx[0][1] + o.jx[1][0] * o.jx[1][1]));
-    o.Hd[2] = ba_sum16(w * (o.jx[0][0] * o.jx[0][2] + o.jx[1][0] * o.jx[1][2]));
-    o.Hd[3] = ba_sum16(w * (o.jx[0][1] * o.jx[0][1] + o.jx[1][1] * o.jx[1][1]));
-    o.Hd[4] = ba_sum16(w * (o.jx[0][1] * o.jx[0][2] + o.jx[1][1] * o.jx[1][2]));
-    o.Hd[5] = ba_sum16(w * (o.jx[0][2] * o.jx[0][2] + o.jx[1][2] * o.jx[1][2]));
+    o.Hd[0] = lanes_sum<16>(w * (o.jx[0][0] * o.jx[0][0] + o.jx[1][0] * o.jx[1][0]));
+    o.Hd[1] = lanes_sum<16>(w * (o.jx[0][0] * o.jx[0][1] + o.jx[1][0] * o.jx[1][1]));
+    o.Hd[2] = lanes_sum<16>(w * (o.jx[0][0] * o.jx[0][2] + o.jx[1][0] * o.jx[1][2]));
+    o.Hd[3] = lanes_sum<16>(w * (o.jx[0][1] * o.jx[0][1] + o.jx[1][1] * o.jx[1][1]));
+    o.Hd[4] = lanes_sum<16>(w * (o.jx[0][1] * o.jx[0][2] + o.jx[1][1] * o.jx[1][2]));
+    o.Hd[5] = lanes_sum<16>(w * (o.jx[0][2] * o.jx[0][2] + o.jx[1][2] * o.jx[1][2]));
 #pragma unroll
-    for (int k = 0; k < 3; ++k) o.gp[k] = ba_sum16(w * (o.jx[0][k] * o.r[0] + o.jx[1][k] * o.r[1]));
+    for (int k = 0; k < 3; ++k) o.gp[k] = lanes_sum<16>(w * (o.jx[0][k] * o.r[0] + o.jx[1][k] * o.r[1]));
     o.Hd[0] += g.lambda * (o.Hd[0] + kBaDiagEps);
     o.Hd[3] += g.lambda * (o.Hd[3] + kBaDiagEps);
     o.Hd[5] += g.lambda * (o.Hd[5] + kBaDiagEps);
@@ -450,7 +393,7 @@ __device__ __forceinline__ void ba_task(int task, int V, int& v1, int& i, int& v
 }
 
 __global__ __launch_bounds__(kRigThreads) void rig_ba_moments_kernel(const BaArgs g) {
-    __shared__ double Ysh[kBaPts * kRigMaxViews * 18];          // H_cp of the tile: [point][view][6][3]
+    __shared__ double Ysh[kBaPts * kViewsMax * 18];          // H_cp of the tile: [point][view][6][3]
     __shared__ double Hish[kBaPts][9];                           // H_pp,d^-1, column by column
     __shared__ double gpsh[kBaPts][3];
     __shared__ unsigned seensh[kBaPts];
@@ -487,7 +430,7 @@ __global__ __launch_bounds__(kRigThreads) void rig_ba_moments_kernel(const BaArg
             Esum += o.e;
             nsum += o.counted ? 1.0 : 0.0;
         }
-        double* Y = Ysh + (pt * kRigMaxViews + lane) * 18;
+        double* Y = Ysh + (pt * kViewsMax + lane) * 18;
 #pragma unroll
         for (int i = 0; i < 6; ++i)
 #pragma unroll
@@ -515,8 +458,8 @@ __global__ __launch_bounds__(kRigThreads) void rig_ba_moments_kernel(const BaArg
             const unsigned need = (1u << tv1[s]) | (1u << tv2[s]);
             for (int q = 0; q < kBaPts; ++q) {       // the tile's points in ascending order
                 if ((seensh[q] & need) != need) continue;
-                const double* y1 = Ysh + (q * kRigMaxViews + tv1[s]) * 18 + ti[s] * 3;
-                const double* y2 = Ysh + (q * kRigMaxViews + tv2[s]) * 18;
+                const double* y1 = Ysh + (q * kViewsMax + tv1[s]) * 18 + ti[s] * 3;
+                const double* y2 = Ysh + (q * kViewsMax + tv2[s]) * 18;
                 const double* Hi = Hish[q];
                 const double z0 = y1[0] * Hi[0] + y1[1] * Hi[3] + y1[2] * Hi[6];
                 const double z1 = y1[0] * Hi[1] + y1[1] * Hi[4] + y1[2] * Hi[7];
@@ -623,7 +566,7 @@ __global__ __launch_bounds__(kRigThreads) void rig_ba_update_kernel(const BaArgs
         double s = 0.0;
 #pragma unroll
         for (int i = 0; i < 6; ++i) s += o.w * (o.jc[0][i] * o.jx[0][a] + o.jc[1][i] * o.jx[1][a]) * d[i];
-        rhs[a] = o.gp[a] + ba_sum16(s);
+        rhs[a] = o.gp[a] + lanes_sum<16>(s);
     }
     if (lane == 0 && p < g.P) {
         const bool moves = o.inside && o.seen;       // any other point passes through as given
@@ -637,13 +580,9 @@ __global__ __launch_bounds__(kRigThreads) void rig_ba_update_kernel(const BaArgs
     }
 }
 
-static int rig_check_shape(const char* who, int V, int N, int J, double conf_min) {
-    ROHM_ARG_CHECK(V >= 2 && V <= kRigMaxViews, "%s: V must be in [2, %d], got %d", who, kRigMaxViews, V);
-    ROHM_ARG_CHECK(N >= 1, "%s: N must be >= 1, got %d", who, N);
-    ROHM_ARG_CHECK(J >= 1, "%s: J must be >= 1, got %d", who, J);
-    ROHM_ARG_CHECK((long long)N * J <= kRigMaxPoints, "%s: N * J must not exceed %lld, got %lld", who, kRigMaxPoints, (long long)N * J);
-    ROHM_ARG_CHECK(isfinite(conf_min), "%s: conf_min must be finite", who);
-    return ROHM_OK;
+static int rig_check(const char* who, int V, int N, int J, double conf_min) {
+    if (int rc = views_check_shape(who, V, 2, N, 1, J)) return rc;
+    return views_check_conf(who, conf_min);
 }
 
 struct BaPlan { int tiles, tiles_per_group, groups, n_tasks, stride; };
@@ -671,14 +610,12 @@ int rig_undistort(const float* keypoints, const double* cams, int V, long long P
 using namespace rohm;
 
 extern "C" long long rohm_rig_pair_ws_bytes(int V, long long P) {
-    ROHM_ARG_CHECK(V >= 2 && V <= kRigMaxViews, "rig_pair_ws_bytes: V must be in [2, %d], got %d", kRigMaxViews, V);
-    ROHM_ARG_CHECK(P >= 1 && P <= kRigMaxPoints, "rig_pair_ws_bytes: P must be in [1, %lld], got %lld", kRigMaxPoints, P);
+    if (int rc = views_check_ws("rig_pair_ws_bytes", V, P)) return rc;
     return (long long)V * P * 16;
 }
 
 extern "C" long long rohm_rig_ba_ws_bytes(int V, long long P) {
-    ROHM_ARG_CHECK(V >= 2 && V <= kRigMaxViews, "rig_ba_ws_bytes: V must be in [2, %d], got %d", kRigMaxViews, V);
-    ROHM_ARG_CHECK(P >= 1 && P <= kRigMaxPoints, "rig_ba_ws_bytes: P must be in [1, %lld], got %lld", kRigMaxPoints, P);
+    if (int rc = views_check_ws("rig_ba_ws_bytes", V, P)) return rc;
     const BaPlan b = ba_plan(V, P);
     return (long long)b.groups * b.stride * 8;
 }
@@ -686,7 +623,7 @@ extern "C" long long rohm_rig_ba_ws_bytes(int V, long long P) {
 extern "C" int rohm_rig_pair_hypotheses(const float* keypoints, const double* cams, const int* pairs, const int* samples, int V, int N, int J,
                                         int Q, int K, double conf_min, double tau_px, void* ws, double* E, long long* counts, int* best,
                                         rohm_stream_t stream) {
-    if (int rc = rig_check_shape("rig_pair_hypotheses", V, N, J, conf_min)) return rc;
+    if (int rc = rig_check("rig_pair_hypotheses", V, N, J, conf_min)) return rc;
     ROHM_ARG_CHECK(Q >= 0, "rig_pair_hypotheses: Q must be >= 0, got %d", Q);
     ROHM_ARG_CHECK(K >= 1, "rig_pair_hypotheses: K must be >= 1, got %d", K);
     ROHM_ARG_CHECK((long long)Q * K <= kRigMaxHyp, "rig_pair_hypotheses: Q * K must not exceed %lld, got %lld", kRigMaxHyp, (long long)Q * K);
@@ -711,14 +648,15 @@ extern "C" int rohm_rig_pair_hypotheses(const float* keypoints, const double* ca
     hipLaunchKernelGGL(rig_hypotheses_kernel, dim3((unsigned)((K + kRigHypPerBlock - 1) / kRigHypPerBlock), (unsigned)Q), dim3(kRigThreads), 0,
                        (hipStream_t)stream, a);
     ROHM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rig_best_kernel, dim3((unsigned)Q), dim3(256), 0, (hipStream_t)stream, counts, K, best);
+    // a degenerate hypothesis counts -1: all of a pair's degenerate gives -1
+    hipLaunchKernelGGL((best_score_kernel<kRigPickThreads, 2, 0ll>), dim3((unsigned)Q), dim3(kRigPickThreads), 0, (hipStream_t)stream, counts, K, best);
     ROHM_LAUNCH_CHECK();
     return ROHM_OK;
 }
 
 extern "C" int rohm_rig_pair_moments(const float* keypoints, const double* cams, const int* pairs, const double* E, int V, int N, int J, int Q,
                                      double conf_min, double tau_px, void* ws, double* moments, rohm_stream_t stream) {
-    if (int rc = rig_check_shape("rig_pair_moments", V, N, J, conf_min)) return rc;
+    if (int rc = rig_check("rig_pair_moments", V, N, J, conf_min)) return rc;
     ROHM_ARG_CHECK(Q >= 0, "rig_pair_moments: Q must be >= 0, got %d", Q);
     ROHM_ARG_CHECK(isfinite(tau_px) && tau_px > 0.0, "rig_pair_moments: tau_px must be finite and > 0, got %g", tau_px);
     if (Q == 0) return ROHM_OK;
@@ -738,7 +676,7 @@ extern "C" int rohm_rig_pair_moments(const float* keypoints, const double* cams,
 }
 
 static int ba_check(const char* who, int V, int N, int J, double conf_min, double sigma_px, double lambda) {
-    if (int rc = rig_check_shape(who, V, N, J, conf_min)) return rc;
+    if (int rc = rig_check(who, V, N, J, conf_min)) return rc;
     ROHM_ARG_CHECK(isfinite(sigma_px) && sigma_px >= 0.0, "%s: sigma_px must be finite and >= 0, got %g", who, sigma_px);
     ROHM_ARG_CHECK(isfinite(lambda) && lambda >= 0.0, "%s: lambda must be finite and >= 0, got %g", who, lambda);
     return ROHM_OK;

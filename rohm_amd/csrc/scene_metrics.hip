@@ -14,24 +14,14 @@
 
 #pragma clang fp contract(off)
 
+#include "reduce.h"      // after the pragma: what it adds is compiled under this file's setting
+
 namespace rohm {
 
 constexpr int kSJ = 22;
 constexpr int kNScene = 11;      // layout documented in include/rohm_hip.h
 constexpr int kSceneMaxT = 800;
 __constant__ int kSFoot[4] = {7, 10, 8, 11};      // eval_prox_egobody.py:189
-
-__device__ __forceinline__ double scene_block_sum(double v, double* sh) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-    for (int o = blockDim.x / 2; o > 0; o >>= 1) {
-        if (tid < o) sh[tid] += sh[tid + o];
-        __syncthreads();
-    }
-    return sh[0];
-}
 
 // correctly rounded float32 square root, as numpy's: the device sqrt is only guaranteed to within an ulp, so its
 // result is moved to the neighbour on the other side of a rounding midpoint when there is one.  A midpoint between two
@@ -183,7 +173,7 @@ __global__ __launch_bounds__(256) void scene_metrics_kernel(const float* __restr
     }
     const double vals[kNScene] = {n_skate, s_acc, s_acc_err, n_pene, s_pene, s_glob, s_loc, s_loc_vis, s_vis, s_loc_occ, s_occ};
     for (int k = 0; k < kNScene; ++k) {
-        const double v = scene_block_sum(vals[k], sh);
+        const double v = block_tree_reduce(vals[k], sh, SumOp());
         if (tid == 0) out[(size_t)b * kNScene + k] = v;
     }
 }

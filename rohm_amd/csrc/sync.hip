@@ -5,14 +5,15 @@
 // reference.
 //
 // The undistortion of every view's points (once per call, into the workspace), the pair test and the Sampson terms are rig.hip's,
-// through epipolar_math.h.  All arithmetic is float64 on the float32 keypoints.  No atomics: every sum has the order of
-// rohm_rig_pair_moments -- thread t takes the points t, t + 256, ..., a xor-butterfly per wave, the four wave partials in wave order.
+// through epipolar_math.h.  All arithmetic is float64 on the float32 keypoints.  No atomics: thread t takes the points t, t + 256,
+// ... in ascending order, and the threads' sums meet in reduce.h's block_reduce, which fixes the rest of the order.
 //
 // rohm_sync_pair_sweep is the plain form: one workgroup of 256 threads per (pair, shift).  A ten-minute recording of four views swept
 // over +-30 frames is 366 workgroups of 4e5 points each; view 1's point and view 2's two brackets are 48 bytes per point out of L2.
 #include "common.h"
 #include "camera_math.h"
 #include "epipolar_math.h"
+#include "reduce.h"
 #include "../../include/provisional/rohm_sync.h"
 
 namespace rohm {
@@ -85,19 +86,7 @@ __global__ __launch_bounds__(kSyncThreads) void sync_sweep_kernel(const SyncSwee
             m[2] += g.sigma2 > 0.0 ? 1.0 : (double)INFINITY;
         }
     }
-#pragma unroll
-    for (int k = 0; k < kSyncOut; ++k) {
-        double v = m[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if ((tid & 63) == 0) shm[tid >> 6][k] = v;
-    }
-    __syncthreads();
-    if (tid < kSyncOut) {
-        double v = shm[0][tid];
-        for (int w = 1; w < kSyncThreads / 64; ++w) v += shm[w][tid];
-        out[tid] = v;
-    }
+    block_reduce<kSyncThreads, kSyncOut>(m, shm, out, SumOfK());
 }
 
 // a bracket that carries a position: finite, with a positive confidence (the track resampler's rule)
@@ -146,32 +135,23 @@ __global__ __launch_bounds__(256) void sync_resample_kernel(const float* __restr
     out[(size_t)i * 3 + 2] = c;
 }
 
-static int sync_check_shape(const char* who, int V, int v_min, int N, int J) {
-    ROHM_ARG_CHECK(V >= v_min && V <= kRigMaxViews, "%s: V must be in [%d, %d], got %d", who, v_min, kRigMaxViews, V);
-    ROHM_ARG_CHECK(N >= 1, "%s: N must be >= 1, got %d", who, N);
-    ROHM_ARG_CHECK(J >= 1, "%s: J must be >= 1, got %d", who, J);
-    ROHM_ARG_CHECK((long long)N * J <= kRigMaxPoints, "%s: N * J must not exceed %lld, got %lld", who, kRigMaxPoints, (long long)N * J);
-    return ROHM_OK;
-}
-
 }  // namespace rohm
 
 using namespace rohm;
 
 extern "C" long long rohm_sync_ws_bytes(int V, long long P) {
-    ROHM_ARG_CHECK(V >= 2 && V <= kRigMaxViews, "sync_ws_bytes: V must be in [2, %d], got %d", kRigMaxViews, V);
-    ROHM_ARG_CHECK(P >= 1 && P <= kRigMaxPoints, "sync_ws_bytes: P must be in [1, %lld], got %lld", kRigMaxPoints, P);
+    if (int rc = views_check_ws("sync_ws_bytes", V, P)) return rc;
     return (long long)V * P * 16;
 }
 
 extern "C" int rohm_sync_pair_sweep(const float* keypoints, const double* cams, const int* pairs, const double* E, const double* shifts, int V,
                                     int N, int J, int Q, int S, double conf_min, double tau_px, double sigma_px, void* ws, double* out,
                                     rohm_stream_t stream) {
-    if (int rc = sync_check_shape("sync_pair_sweep", V, 2, N, J)) return rc;
+    if (int rc = views_check_shape("sync_pair_sweep", V, 2, N, 1, J)) return rc;
     ROHM_ARG_CHECK(Q >= 0, "sync_pair_sweep: Q must be >= 0, got %d", Q);
     ROHM_ARG_CHECK(S >= 1, "sync_pair_sweep: S must be >= 1, got %d", S);
     ROHM_ARG_CHECK((long long)Q * S <= kSyncMaxCells, "sync_pair_sweep: Q * S must not exceed %lld, got %lld", kSyncMaxCells, (long long)Q * S);
-    ROHM_ARG_CHECK(isfinite(conf_min), "sync_pair_sweep: conf_min must be finite");
+    if (int rc = views_check_conf("sync_pair_sweep", conf_min)) return rc;
     ROHM_ARG_CHECK(isfinite(tau_px) && tau_px > 0.0, "sync_pair_sweep: tau_px must be finite and > 0, got %g", tau_px);
     ROHM_ARG_CHECK(isfinite(sigma_px) && sigma_px >= 0.0, "sync_pair_sweep: sigma_px must be finite and >= 0, got %g", sigma_px);
     if (Q == 0) return ROHM_OK;
@@ -194,7 +174,7 @@ extern "C" int rohm_sync_pair_sweep(const float* keypoints, const double* cams, 
 }
 
 extern "C" int rohm_sync_resample(const float* keypoints, const double* shifts, int V, int N, int J, float* out, rohm_stream_t stream) {
-    if (int rc = sync_check_shape("sync_resample", V, 1, N, J)) return rc;
+    if (int rc = views_check_shape("sync_resample", V, 1, N, 1, J)) return rc;
     ROHM_ARG_CHECK(keypoints, "sync_resample: keypoints is null");
     ROHM_ARG_CHECK(shifts, "sync_resample: shifts is null");
     ROHM_ARG_CHECK(out, "sync_resample: out is null");

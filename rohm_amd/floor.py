@@ -33,9 +33,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, lib, ptr, stream_ptr
+from ._lib import UP_AXIS, check, lib, ptr, stream_ptr, up_index as _up
 
-UP_AXIS = {'z': 2, 'y': 1}
 TOES = (10, 11)
 N_MOMENTS = 11
 ESTIMATE_FIELDS = ('normal', 'offset', 'cam2world', 'floor_height', 'candidates', 'support', 'under', 'rms', 'extent', 'hypothesis',
@@ -71,12 +70,6 @@ class FloorEstimate:
 
 
 # ---- host logic (float64 numpy; no device) ---------------------------------------------------------------------------------
-def _up(up_axis):
-    if up_axis not in UP_AXIS:
-        raise ValueError(f"up_axis must be 'z' or 'y', got {up_axis!r}")
-    return UP_AXIS[up_axis]
-
-
 def draw_triples(P, K, seed):
     """[K, 3] int32 indices into the P candidates: the same seed and the same track give the same hypotheses."""
     if P < 1 or K < 0:

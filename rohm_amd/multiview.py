@@ -64,15 +64,24 @@ class Triangulation:
 
 
 # ---- the kernels' wrappers -----------------------------------------------------------------------------------------------------
-_hip = functools.partial(_lib.hip_tensor, kernels='the multiview kernels take')
+_TAKE = 'the multiview kernels take'
+_hip = functools.partial(_lib.hip_tensor, kernels=_TAKE)
 
 
-def _operands(keypoints, cams):
-    kp = _hip(keypoints, 'keypoints').detach().float().contiguous()
+def keypoints_operand(keypoints, kernels):
+    """keypoints [V,N,J,3] as a contiguous float32 HIP tensor -> (kp, V, N, J); `kernels` as `_lib.hip_tensor` takes it.  `rig` and
+    `sync` check their operands here too."""
+    kp = _lib.hip_tensor(keypoints, 'keypoints', kernels).detach().float().contiguous()
     if kp.dim() != 4 or kp.shape[3] != 3 or kp.shape[2] < 1:
         raise ValueError(f'keypoints must be [V, N, J, 3], got {list(kp.shape)}')
     V, N, J = (int(s) for s in kp.shape[:3])
-    cm = _hip(cams, 'cams').detach().double().contiguous()
+    return kp, V, N, J
+
+
+def views_operands(keypoints, cams, kernels):
+    """`keypoints_operand` and cams [V,24] (`pack_cameras`) as a contiguous float64 HIP tensor -> (kp, cm, V, N, J)."""
+    kp, V, N, J = keypoints_operand(keypoints, kernels)
+    cm = _lib.hip_tensor(cams, 'cams', kernels).detach().double().contiguous()
     if tuple(cm.shape) != (V, CAM):
         raise ValueError(f'cams must be [{V}, {CAM}] (pack_cameras), got {list(cm.shape)}')
     return kp, cm, V, N, J
@@ -83,7 +92,7 @@ def triangulate(keypoints, cams, conf_min=CONF_MIN, tau_px=TAU_PX, min_angle_deg
     """`rohm_mv_triangulate`: keypoints [V,N,J,3] float32 (x, y in pixels as detected, confidence), cams [V,24] float64
     (`pack_cameras`), rigid [12] or [3,4] float64 or None (world -> output frame, R|t; None leaves the world frame), HIP tensors
     -> `Triangulation`.  One launch, no synchronisation, nothing read back; there is no CPU path."""
-    kp, cm, V, N, J = _operands(keypoints, cams)
+    kp, cm, V, N, J = views_operands(keypoints, cams, _TAKE)
     rg = None
     if rigid is not None:
         rg = _hip(rigid, 'rigid').detach().double()
@@ -109,7 +118,7 @@ def view_residuals(joints_world, keypoints, cams, conf_min=CONF_MIN):
     """`rohm_mv_residuals`: joints_world [N,J,3] float64 in the world frame, keypoints and cams as `triangulate` (HIP tensors) ->
     resid [V,N,J] float64 on the device: the pixel distance between each detection as given and the joint projected with the
     forward distortion model, NaN where the view is unobserved, the joint is NaN or it lies behind the camera."""
-    kp, cm, V, N, J = _operands(keypoints, cams)
+    kp, cm, V, N, J = views_operands(keypoints, cams, _TAKE)
     jw = _hip(joints_world, 'joints_world').detach().double().contiguous()
     if tuple(jw.shape) != (N, J, 3):
         raise ValueError(f'joints_world must be [{N}, {J}, 3], got {list(jw.shape)}')
@@ -146,6 +155,21 @@ def pack_cameras(camera_mtx, world2cam, dist_coeffs=None):
             raise ValueError(f'dist_coeffs must be [{V},5] and finite, got {D.shape}')
         cams[:, 16:21] = D
     return cams
+
+
+def _read_time_key(d, N):
+    """'fps' or 'times', whichever of the two a views file's dict gives, validated; `sync.frame_rate` reads it here too."""
+    if ('fps' in d) == ('times' in d):
+        raise ValueError('views: give exactly one of fps and times')
+    if 'fps' in d:
+        fps = np.asarray(d['fps'], dtype=np.float64)
+        if fps.size != 1 or not np.isfinite(fps).all() or float(fps.reshape(-1)[0]) <= 0:
+            raise ValueError(f'views: fps must be one positive number, got {d["fps"]!r}')
+        return 'fps'
+    times = np.asarray(d['times'], dtype=np.float64)
+    if times.shape != (N,) or not np.isfinite(times).all() or (np.diff(times) <= 0).any():
+        raise ValueError(f'views: times must be [{N}], finite and strictly increasing')
+    return 'times'
 
 
 def read_views(views, min_views=2):
@@ -188,16 +212,7 @@ def read_views(views, min_views=2):
         pack_cameras(K, W, dist)
     except ValueError as e:
         raise ValueError(f'views: {e}') from None
-    if ('fps' in d) == ('times' in d):
-        raise ValueError('views: give exactly one of fps and times')
-    if 'fps' in d:
-        fps = np.asarray(d['fps'], dtype=np.float64)
-        if fps.size != 1 or not np.isfinite(fps).all() or float(fps.reshape(-1)[0]) <= 0:
-            raise ValueError(f'views: fps must be one positive number, got {d["fps"]!r}')
-    else:
-        times = np.asarray(d['times'], dtype=np.float64)
-        if times.shape != (N,) or not np.isfinite(times).all() or (np.diff(times) <= 0).any():
-            raise ValueError(f'views: times must be [{N}], finite and strictly increasing')
+    time_key = _read_time_key(d, N)
     up = None
     if 'world_up_axis' in d:
         up = str(np.asarray(d['world_up_axis']).reshape(-1)[0])
@@ -214,7 +229,7 @@ def read_views(views, min_views=2):
     if 'frame_names' in d and np.asarray(d['frame_names']).shape != (N,):
         raise ValueError(f'views: frame_names must be [{N}], got {np.asarray(d["frame_names"]).shape}')
     out = {'keypoints': np.ascontiguousarray(kp), 'camera_mtx': K, 'world2cam': W, 'dist_coeffs': dist, 'world_up_axis': up, 'floor_height': floor,
-           'time_key': 'fps' if 'fps' in d else 'times'}
+           'time_key': time_key}
     out[out['time_key']] = d[out['time_key']]
     out.update({k: d[k] for k in ('frame_names', 'recording_name') if k in d})
     return out

@@ -25,11 +25,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, lib, ptr, stream_ptr
+from ._lib import UP_AXIS, check, lib, ptr, stream_ptr, up_index as _up
 
 COLUMNS = ('reproj_px', 'reproj_max_px', 'reproj_n', 'skate', 'accel', 'pene', 'dev_vis', 'dev_occ', 'n_vis', 'gap')
 N_TOTALS = 15
-UP_AXIS = {'z': 2, 'y': 1}
 GROUPS = ('observed', 'infilled')
 _LOWER_IS_WORSE = ('pene',)
 
@@ -143,12 +142,6 @@ def _tensor(x, name, shape, dtype):
     if tuple(x.shape) != shape:
         raise ValueError(f'{name} must be {list(shape)}, got {list(x.shape)}')
     return x.detach().to(dtype).contiguous()
-
-
-def _up(up_axis):
-    if up_axis not in UP_AXIS:
-        raise ValueError(f"up_axis must be 'z' or 'y', got {up_axis!r}")
-    return UP_AXIS[up_axis]
 
 
 def track_quality(joints, fps=30.0, up_axis='z', floor_height=None, scene2cam=None, focal=None, center=None, keypoints=None,

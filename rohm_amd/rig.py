@@ -49,7 +49,8 @@ LAMBDA0, LAMBDA_MIN, LAMBDA_MAX, TRIES = 1e-3, 1e-9, 1e8, 8
 # SMPL joints: the shins, the forearms and the upper arms; BODY_25 has true counterparts for all of them
 BONES = ((4, 7), (5, 8), (16, 18), (17, 19), (18, 20), (19, 21))
 _TRI = [(i, j) for i in range(9) for j in range(i, 9)]
-_hip = functools.partial(_lib.hip_tensor, kernels='the rig kernels take')
+_TAKE = 'the rig kernels take'
+_hip = functools.partial(_lib.hip_tensor, kernels=_TAKE)
 
 
 # ---- the kernels' wrappers -----------------------------------------------------------------------------------------------------
@@ -71,17 +72,6 @@ def _workspace(nbytes, dev):
     return torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.float64)
 
 
-def _operands(keypoints, cams):
-    kp = _hip(keypoints, 'keypoints').detach().float().contiguous()
-    if kp.dim() != 4 or kp.shape[3] != 3 or kp.shape[2] < 1:
-        raise ValueError(f'keypoints must be [V, N, J, 3], got {list(kp.shape)}')
-    V, N, J = (int(s) for s in kp.shape[:3])
-    cm = _hip(cams, 'cams').detach().double().contiguous()
-    if tuple(cm.shape) != (V, CAM):
-        raise ValueError(f'cams must be [{V}, {CAM}] (multiview.pack_cameras), got {list(cm.shape)}')
-    return kp, cm, V, N, J
-
-
 def _pairs(pairs):
     pr = _hip(pairs, 'pairs').detach().to(torch.int32).contiguous()
     if pr.dim() != 2 or pr.shape[1] != 2:
@@ -93,7 +83,7 @@ def pair_hypotheses(keypoints, cams, pairs, samples, conf_min=CONF_MIN, tau_px=T
     """`rohm_rig_pair_hypotheses`: keypoints [V,N,J,3] float32, cams [V,24] float64 (the intrinsics are read), pairs [Q,2] int32,
     samples [Q,K,8] int32 (HIP tensors) -> E [Q,K,9] float64, counts [Q,K,2] int64 (inliers, common points), best [Q] int32.  Three
     launches, no synchronisation, nothing read back; there is no CPU path."""
-    kp, cm, V, N, J = _operands(keypoints, cams)
+    kp, cm, V, N, J = multiview.views_operands(keypoints, cams, _TAKE)
     pr, Q = _pairs(pairs)
     sm = _hip(samples, 'samples').detach().to(torch.int32).contiguous()
     if sm.dim() != 3 or sm.shape[0] != Q or sm.shape[2] != 8:
@@ -112,9 +102,9 @@ def pair_hypotheses(keypoints, cams, pairs, samples, conf_min=CONF_MIN, tau_px=T
 def pair_moments(keypoints, cams, pairs, E, conf_min=CONF_MIN, tau_px=TAU_PX):
     """`rohm_rig_pair_moments`: as above with E [Q,9] float64 -> moments [Q,47] float64: per pair the inliers' count, sum d^2 and
     the 45 upper-triangle sums of row^T row.  Two launches."""
-    kp, cm, V, N, J = _operands(keypoints, cams)
+    kp, cm, V, N, J = multiview.views_operands(keypoints, cams, _TAKE)
     pr, Q = _pairs(pairs)
-    Ed = _lib.hip_rows(E, 'E', (Q, 9), 'the rig kernels take')
+    Ed = _lib.hip_rows(E, 'E', (Q, 9), _TAKE)
     out = torch.empty(Q, N_MOM, device=kp.device, dtype=torch.float64)
     with torch.cuda.device(kp.device):
         ws = _workspace(pair_ws_bytes(V, N * J), kp.device)
@@ -134,7 +124,7 @@ def ba_moments(keypoints, cams, points, conf_min=CONF_MIN, sigma_px=SIGMA_PX, la
     """`rohm_rig_ba_moments`: cams [V,24] (the current rig), points [N J,3] float64 (NaN rows are outside the problem) -> S
     [6V,6V], r [6V], stats [2] = (E, the number of observations): the camera system of one Levenberg-Marquardt try with the points
     eliminated.  Two launches."""
-    kp, cm, V, N, J = _operands(keypoints, cams)
+    kp, cm, V, N, J = multiview.views_operands(keypoints, cams, _TAKE)
     X, dev = _points(points, N, J), kp.device
     S = torch.empty(6 * V, 6 * V, device=dev, dtype=torch.float64)
     r = torch.empty(6 * V, device=dev, dtype=torch.float64)
@@ -149,9 +139,9 @@ def ba_moments(keypoints, cams, points, conf_min=CONF_MIN, sigma_px=SIGMA_PX, la
 def ba_update(keypoints, cams, points, dc, conf_min=CONF_MIN, sigma_px=SIGMA_PX, lam=LAMBDA0):
     """`rohm_rig_ba_update`: the same operands and dc [V,6] float64 (delta omega, delta t per camera) -> points_new (the shape of
     `points`; a point outside the problem passes through), cams_new [V,24].  One launch."""
-    kp, cm, V, N, J = _operands(keypoints, cams)
+    kp, cm, V, N, J = multiview.views_operands(keypoints, cams, _TAKE)
     X, dev = _points(points, N, J), kp.device
-    d = _lib.hip_rows(dc, 'dc', (V, 6), 'the rig kernels take')
+    d = _lib.hip_rows(dc, 'dc', (V, 6), _TAKE)
     Xn, cn = torch.empty_like(X), torch.empty_like(cm)
     with torch.cuda.device(dev):
         check(lib().rohm_rig_ba_update(ptr(kp), ptr(cm), ptr(X), ptr(d), V, N, J, float(conf_min), float(sigma_px), float(lam), ptr(Xn), ptr(cn),

@@ -56,7 +56,8 @@ GRID, HALF = 16, 16                                    # the fine sweep: est + k
 REFITS = 2
 PAIRS_PER_CALL = 8                                     # two views per pair in a RANSAC call: the 16-view limit
 UNIFORM_RTOL = 1e-6
-_hip = functools.partial(_lib.hip_tensor, kernels='the sync kernels take')
+_TAKE = 'the sync kernels take'
+_hip = functools.partial(_lib.hip_tensor, kernels=_TAKE)
 
 
 # ---- the kernels' wrappers -----------------------------------------------------------------------------------------------------
@@ -72,9 +73,9 @@ def pair_sweep(keypoints, cams, pairs, E, shifts, conf_min=CONF_MIN, tau_px=TAU_
     float64, shifts [Q,S] float64 in frames (HIP tensors) -> out [Q,S,4] float64: per (pair, shift) the common points, the inliers,
     sum d^2 / (d^2 + sigma_px^2) over the common points and sum d^2 over the inliers.  Two launches, no synchronisation, nothing read
     back; there is no CPU path."""
-    kp, cm, V, N, J = rig._operands(keypoints, cams)
+    kp, cm, V, N, J = multiview.views_operands(keypoints, cams, rig._TAKE)      # the views and the pairs are rig's operands, refused in rig's words
     pr, Q = rig._pairs(pairs)
-    Ed = _lib.hip_rows(E, 'E', (Q, 9), 'the sync kernels take')
+    Ed = _lib.hip_rows(E, 'E', (Q, 9), _TAKE)
     sh = _hip(shifts, 'shifts').detach().double().contiguous()
     if sh.dim() != 2 or sh.shape[0] != Q or sh.shape[1] < 1:
         raise ValueError(f'shifts must be [{Q}, S] with S >= 1, got {list(sh.shape)}')
@@ -91,11 +92,8 @@ def resample_views(keypoints, shifts):
     """`rohm_sync_resample`: keypoints [V,N,J,3] float32, shifts [V] float64 in frames (HIP tensors) -> [V,N,J,3] float32: view v at
     the frame index n + shifts[v] (x, y linear in float64, the confidence the smaller of the two brackets', zeros outside the
     recording; a zero shift copies the bits).  One launch."""
-    kp = _hip(keypoints, 'keypoints').detach().float().contiguous()
-    if kp.dim() != 4 or kp.shape[3] != 3 or kp.shape[2] < 1:
-        raise ValueError(f'keypoints must be [V, N, J, 3], got {list(kp.shape)}')
-    V, N, J = (int(s) for s in kp.shape[:3])
-    sh = _lib.hip_rows(shifts, 'shifts', (V,), 'the sync kernels take')
+    kp, V, N, J = multiview.keypoints_operand(keypoints, _TAKE)
+    sh = _lib.hip_rows(shifts, 'shifts', (V,), _TAKE)
     out = torch.empty_like(kp)
     with torch.cuda.device(kp.device):
         check(lib().rohm_sync_resample(ptr(kp), ptr(sh), V, N, J, ptr(out), stream_ptr(kp.device)), 'rohm_sync_resample')
@@ -343,16 +341,9 @@ def synchronise(keypoints, camera_mtx, dist_coeffs=None, fps=30.0, world2cam=Non
 def frame_rate(d, N):
     """The common, uniform frame rate of a views file's arrays: `fps`, or `times` [N] uniform within 1e-6 relative; anything else
     is refused by name."""
-    if ('fps' in d) == ('times' in d):
-        raise ValueError('views: give exactly one of fps and times')
-    if 'fps' in d:
-        fps = np.asarray(d['fps'], dtype=np.float64)
-        if fps.size != 1 or not np.isfinite(fps).all() or float(fps.reshape(-1)[0]) <= 0:
-            raise ValueError(f'views: fps must be one positive number, got {d["fps"]!r}')
-        return float(fps.reshape(-1)[0])
+    if multiview._read_time_key(d, N) == 'fps':
+        return float(np.asarray(d['fps'], dtype=np.float64).reshape(-1)[0])
     times = np.asarray(d['times'], dtype=np.float64)
-    if times.shape != (N,) or not np.isfinite(times).all() or (np.diff(times) <= 0).any():
-        raise ValueError(f'views: times must be [{N}], finite and strictly increasing')
     if N < 2:
         raise ValueError('views: times of one frame give no frame rate; give fps')
     step = (times[-1] - times[0]) / (N - 1)
