@@ -338,8 +338,13 @@ size_t rohm_posenet_status_offset(const rohm_posenet_t* h, int B, int T);
  * (ROHM_POSENET_CHAIN=0: one launch per GEMM); bit 5: ... and attention too -- the whole encoder stack of a forward is one launch
  * (`encoder_stack_kernel`, the default from 32 clips on; ROHM_POSENET_CHAIN=layer keeps bit 4 without bit 5).  Bits 4 / 5 say what
  * the handle WOULD launch where the shape qualifies (whole clips, B >= 32 or ROHM_POSENET_CHAIN_ANY=1); they need bit 0.
- * ROHM_EXCHANGE_GUARD=off skips the guard, =probe skips its environment shortcut. */
+ * ROHM_EXCHANGE_GUARD=off skips the guard, =probe skips its environment shortcut.
+ * The chain and the stack address every operand as a scalar base plus a 32-bit byte offset per lane, so they run only where each
+ * operand of the call -- activations of M = B * (T + 1) rows and up to 3 * d_model columns, the packed input, the weights -- is
+ * smaller than 2^31 bytes; rohm_posenet_stack_addressable is that predicate (1 = fits).  A larger call runs one launch per GEMM.
+ * At B = 128 the largest operand is 113 MB, so no supported batch size comes near the bound. */
 int rohm_posenet_exchange_mode(const rohm_posenet_t* h);
+int rohm_posenet_stack_addressable(long long M, int d_model, int d_ff, int k_pack);
 const char* rohm_posenet_exchange_guard(const rohm_posenet_t* h);
 /* on = 0: from now on this handle runs the exchange-free launches (GEMM + LayerNorm kernel pair, plain output-head tiles) -- what the
  * sampling loops do, before re-running the chunk, when rohm_posenet_exchange_status reports a failure.  on = 1: back to what the

@@ -115,6 +115,7 @@ SIGNATURES = {
     'rohm_posenet_exchange_guard': (C.c_char_p, [C.c_void_p]),
     'rohm_posenet_set_exchange': (C.c_int, [C.c_void_p, C.c_int]),
     'rohm_posenet_inject_exchange_fault': (C.c_int, [C.c_void_p, C.c_int]),
+    'rohm_posenet_stack_addressable': (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int]),
     'rohm_posenet_stack_timeline_bytes': (C.c_size_t, [C.c_int]),
     'rohm_posenet_set_stack_timeline': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
     'rohm_output_process_scratch_bytes': (C.c_size_t, []),

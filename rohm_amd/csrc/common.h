@@ -249,6 +249,9 @@ int launch_encoder_stack(const StackParams& p, hipStream_t s);
 int encoder_chain_parts(int M, int D, int F);      // column tiles per clip (4 or 8), 0 = no chain form for this shape
 bool encoder_chain_pays(int B);                    // whole rounds of persistent workgroups: is the chain / stack the faster plan for B clips?
 size_t encoder_chain_flag_bytes(int M);
+// The chain and the stack address their operands as base + 32-bit byte offset: does every operand of M rows (d_model D, d_ff F, packed
+// input of k_pack columns) stay below 2^31 bytes?  (B = 128: the widest, [M, 3 D], is 113 MB.)
+bool encoder_chain_addressable(long long M, int D, int F, int k_pack);
 int launch_encoder_chain(const ChainParams& p, hipStream_t s);
 // Is `s` recording a hipGraph?
 bool stream_is_capturing(hipStream_t s);

@@ -58,23 +58,65 @@ struct PhaseArgs {
 // output element is the same dot product in the same k order as in the 384-column slice of the plain tile.
 __device__ __forceinline__ int head_row(int n0, int t) { return ((t % 96) >> 5) * 512 + n0 + (t / 96) * 32 + (t & 31); }
 
+// Staging addresses of the LDS-DMA: a buffer descriptor over the operand from the tile's first row (operand + clip / part displacement,
+// four SGPRs, built once per phase), ONE 32-bit per-lane byte offset, and the piece / K-chunk displacement as the instruction's scalar
+// offset -- a piece or chunk step is one scalar add where it was a 64-bit add per lane and piece.  Pass i moves unit u = tid + 256 i:
+// row u / 8 = tid / 8 + 32 i, and the swizzled slot (u & 7) ^ ((row >> 1) & 7) is the same for every pass of a lane (32 rows apart:
+// (row >> 1) & 7 does not move).  So the lane offset depends on tid and the leading dimension only.  32 bits: offsets are relative
+// to the tile's first row (a few MB at most), and encoder_chain_addressable keeps every whole operand below 2^31 bytes on the host.
+typedef __amdgpu_buffer_rsrc_t StageRsrc;
+__device__ __forceinline__ StageRsrc stage_rsrc(const float* base) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, 0x7fffffff, 0x00020000);
+}
+__device__ __forceinline__ unsigned stage_lane_off(int tid, int ld) {
+    return ((unsigned)(tid >> 3) * (unsigned)ld + (unsigned)((((tid & 7) ^ ((tid >> 4) & 7))) << 2)) * 4u;
+}
+// A scalar offset hipcc must take as it stands: left alone it hoists chunk-invariant piece displacements out of the K loop, one SGPR
+// per piece, into a kernel that spills SGPRs already.  Chained through this, piece i's offset is piece i - 1's plus a step.
+__device__ __forceinline__ int scalar_off(int v) { asm("" : "+s"(v)); return v; }
+// first row of pass i relative to the tile's: 32 i, or HEAD's (head_row of t = 32 i + tid / 8 is head_row(n0, 32 i) + tid / 8 - n0)
+template <bool HEAD>
+__device__ __forceinline__ constexpr int piece_row(int i) { return HEAD ? (i % 3) * 512 + (i / 3) * 32 : 32 * i; }
+template <bool HEAD>
+__device__ __forceinline__ constexpr int piece_step(int i) { return piece_row<HEAD>(i) - piece_row<HEAD>(i > 0 ? i - 1 : 0); }
+template <int AUX>
+__device__ __forceinline__ void stage16(StageRsrc rs, float* dst, unsigned lane_off, int soff) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)dst, 16, (int)lane_off, soff, 0, AUX);
+}
+
 // Issue the first two K chunks of a phase's weight tile (rows n0 .. n0 + BN of W, or HEAD's rows) into the two W buffers:
 // 2 x BN * 8 / 256 LDS-DMA instructions per wave, no register staging.  Called while the PREVIOUS phase's epilogue is still to run.
-template <int BN, bool HEAD = false>
+// SOFF: the scalar-offset addressing above (the kernels pick per G, like REFETCH: measured +1.6 % at B = 64 with 4 parts per clip,
+// -0.4 % at B = 32 with 8, NOTES 13.3); else a 64-bit pointer per lane and piece.
+template <int BN, bool HEAD = false, bool SOFF = false>
 __device__ __forceinline__ void prefetch_w(const float* W, int ldw, int n0, float* smem, int tid, int wave_u) {
     constexpr int B_ITERS = BN * 8 / 256;
     float* Bs = smem + 2 * BM * BK;
+    if constexpr (!SOFF) {
 #pragma unroll
-    for (int buf = 0; buf < 2; ++buf)
+        for (int buf = 0; buf < 2; ++buf)
+#pragma unroll
+            for (int i = 0; i < B_ITERS; ++i) {
+                const int u = tid + i * 256;
+                const int row = u >> 3;
+                const int slot = (u & 7) ^ ((row >> 1) & 7);
+                const float* src = W + (size_t)(HEAD ? head_row(n0, row) : n0 + row) * ldw + slot * 4 + buf * BK;
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                                 (__attribute__((address_space(3))) void*)(Bs + buf * (BN * BK) + (i * 256 + wave_u) * 4), 16, 0, 0);
+            }
+        return;
+    }
+    const unsigned off = stage_lane_off(tid, ldw);
+    const StageRsrc rs = stage_rsrc(W + (size_t)n0 * ldw);
+#pragma unroll
+    for (int buf = 0; buf < 2; ++buf) {
+        int so = 0;
 #pragma unroll
         for (int i = 0; i < B_ITERS; ++i) {
-            const int u = tid + i * 256;
-            const int row = u >> 3;
-            const int slot = (u & 7) ^ ((row >> 1) & 7);
-            const float* src = W + (size_t)(HEAD ? head_row(n0, row) : n0 + row) * ldw + slot * 4 + buf * BK;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(Bs + buf * (BN * BK) + (i * 256 + wave_u) * 4), 16, 0, 0);
+            so = scalar_off(i == 0 ? buf * BK * 4 : so + piece_step<HEAD>(i) * ldw * 4);
+            stage16<0>(rs, Bs + buf * (BN * BK) + (i * 256 + wave_u) * 4, off, so);
         }
+    }
 }
 
 // The G workgroups of a clip meet: everybody's stores of the phase are in L2 before anybody reads them.  flags[k] = (XCD id + 1) << 32
@@ -149,37 +191,70 @@ __device__ __forceinline__ void gemm_phase(const PhaseArgs& p, float* smem, cons
     // ---- staging -----------------------------------------------------------------------------------------------------------
     // gemm_tile.h's geometry (unit_slot, unit_dst) and fragment read, written out: called through the header from here and from
     // prefetch_w, the instruction stream of all four kernels moves (profiles/gemm_tile_resources.md)
+    constexpr bool SOFF = !REFETCH;      // both are the kernels' choice per G: 4 parts per clip take the scalar-offset addressing
     const float* a_src[A_ITERS];
-#pragma unroll
-    for (int i = 0; i < A_ITERS; ++i) {
-        const int u = tid + i * 256;
-        const int row = (u < A_UNITS) ? (u >> 3) : 0;
-        const int slot = (u & 7) ^ ((row >> 1) & 7);
-        a_src[i] = p.A + (size_t)(m0 + row) * p.lda + slot * 4;
-    }
     const float* b_src[B_ITERS];
+    if constexpr (!SOFF) {
 #pragma unroll
-    for (int i = 0; i < B_ITERS; ++i) {
-        const int u = tid + i * 256;
-        const int row = u >> 3;
-        const int slot = (u & 7) ^ ((row >> 1) & 7);
-        b_src[i] = p.W + (size_t)(HEAD ? head_row(n0, row) : n0 + row) * p.ldw + slot * 4;
+        for (int i = 0; i < A_ITERS; ++i) {
+            const int u = tid + i * 256;
+            const int row = (u < A_UNITS) ? (u >> 3) : 0;
+            const int slot = (u & 7) ^ ((row >> 1) & 7);
+            a_src[i] = p.A + (size_t)(m0 + row) * p.lda + slot * 4;
+        }
+#pragma unroll
+        for (int i = 0; i < B_ITERS; ++i) {
+            const int u = tid + i * 256;
+            const int row = u >> 3;
+            const int slot = (u & 7) ^ ((row >> 1) & 7);
+            b_src[i] = p.W + (size_t)(HEAD ? head_row(n0, row) : n0 + row) * p.ldw + slot * 4;
+        }
     }
+    const unsigned a_off = stage_lane_off(tid, p.lda), b_off = stage_lane_off(tid, p.ldw);
+    const StageRsrc a_rs = stage_rsrc(p.A + (size_t)m0 * p.lda);
+    const StageRsrc b_rs = stage_rsrc(p.W + (size_t)n0 * p.ldw);
     auto dma_a = [&](int buf, int k0) {
+        if constexpr (!SOFF) {
+#pragma unroll
+            for (int piece = 0; piece < A_ITERS; ++piece) {
+                float* dst = As + buf * (BM * BK) + (piece * 256 + wave_u) * 4;
+                if (piece == A_ITERS - 1 && A_UNITS % 256 != 0)
+                    dst = (wave_u < A_UNITS - (A_ITERS - 1) * 256) ? dst : lds_dummy + (wave_u & 64) * 4;
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_src[piece] + k0),
+                                                 (__attribute__((address_space(3))) void*)dst, 16, 0, AUX);
+            }
+            return;
+        }
+        const int s0 = scalar_off(k0 * 4);
+        int so = s0;
 #pragma unroll
         for (int piece = 0; piece < A_ITERS; ++piece) {
             float* dst = As + buf * (BM * BK) + (piece * 256 + wave_u) * 4;
-            if (piece == A_ITERS - 1 && A_UNITS % 256 != 0)
-                dst = (wave_u < A_UNITS - (A_ITERS - 1) * 256) ? dst : lds_dummy + (wave_u & 64) * 4;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_src[piece] + k0),
-                                             (__attribute__((address_space(3))) void*)dst, 16, 0, AUX);
+            if (piece > 0) so = so + 32 * 4 * p.lda;
+            if (piece == A_ITERS - 1 && A_UNITS % 256 != 0) {
+                // the waves past the image fetch a (valid) dummy row -- pass 0's -- into the landing zone
+                const bool in = wave_u < A_UNITS - (A_ITERS - 1) * 256;
+                dst = in ? dst : lds_dummy + (wave_u & 64) * 4;
+                so = in ? so : s0;
+            }
+            so = scalar_off(so);
+            stage16<AUX>(a_rs, dst, a_off, so);
         }
     };
     auto dma_b = [&](int buf, int k0) {
+        if constexpr (!SOFF) {
 #pragma unroll
-        for (int i = 0; i < B_ITERS; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_src[i] + k0),
-                                             (__attribute__((address_space(3))) void*)(Bs + buf * (BN * BK) + (i * 256 + wave_u) * 4), 16, 0, 0);
+            for (int i = 0; i < B_ITERS; ++i)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_src[i] + k0),
+                                                 (__attribute__((address_space(3))) void*)(Bs + buf * (BN * BK) + (i * 256 + wave_u) * 4), 16, 0, 0);
+            return;
+        }
+        int so = 0;
+#pragma unroll
+        for (int i = 0; i < B_ITERS; ++i) {
+            so = scalar_off(i == 0 ? k0 * 4 : so + piece_step<HEAD>(i) * p.ldw * 4);
+            stage16<0>(b_rs, Bs + buf * (BN * BK) + (i * 256 + wave_u) * 4, b_off, so);
+        }
     };
 
     // ---- accumulators and fragments ----------------------------------------------------------------------------------------------
@@ -736,18 +811,18 @@ __global__ __launch_bounds__(256) void encoder_chain_kernel(ChainParams p) {
     // ---- A: y = norm1(h + ctx . Wo^T + bo) ---------------------------------------------------------------------------------------
     a.A = p.ctx; a.lda = p.D; a.W = p.out_w; a.ldw = p.D; a.C = p.y; a.ldc = p.D; a.K = p.D; a.bias = p.out_b;
     a.R = p.h; a.ldr = p.D; a.gamma = p.n1_w; a.beta = p.n1_b; a.n0 = tn * BNL; a.tag28 = ep & 0x0fffffffu; a.fault = p.fault & 1;
-    gemm_phase<BNL, EPI_BIAS_RES_LN, false, false, G == 8>(a, smem, tid, [&]() { prefetch_w<BNF>(p.l1_w, p.D, tn * BNF, smem, tid, wave_u); });
+    gemm_phase<BNL, EPI_BIAS_RES_LN, false, false, G == 8>(a, smem, tid, [&]() { prefetch_w<BNF, false, G == 4>(p.l1_w, p.D, tn * BNF, smem, tid, wave_u); });
     group_sync(flags, tn, G, ep, xcc1, p.xln_err, tid);
 
     // ---- B: ff = gelu(y . W1^T + b1) ---------------------------------------------------------------------------------------------
     a.A = p.y; a.lda = p.D; a.W = p.l1_w; a.ldw = p.D; a.C = p.ff; a.ldc = p.F; a.K = p.D; a.bias = p.l1_b; a.n0 = tn * BNF;
-    gemm_phase<BNF, EPI_BIAS_GELU, true, true, G == 8>(a, smem, tid, [&]() { prefetch_w<BNL>(p.l2_w, p.F, tn * BNL, smem, tid, wave_u); });
+    gemm_phase<BNF, EPI_BIAS_GELU, true, true, G == 8>(a, smem, tid, [&]() { prefetch_w<BNL, false, G == 4>(p.l2_w, p.F, tn * BNL, smem, tid, wave_u); });
     group_sync(flags + 8, tn, G, ep, xcc1, p.xln_err, tid);
 
     // ---- C: h = norm2(y + ff . W2^T + b2) ----------------------------------------------------------------------------------------
     a.A = p.ff; a.lda = p.F; a.W = p.l2_w; a.ldw = p.F; a.C = p.h; a.ldc = p.D; a.K = p.F; a.bias = p.l2_b;
     a.R = p.y; a.ldr = p.D; a.gamma = p.n2_w; a.beta = p.n2_b; a.n0 = tn * BNL; a.tag28 = (ep + 1u) & 0x0fffffffu; a.fault = (p.fault >> 1) & 1;
-    gemm_phase<BNL, EPI_BIAS_RES_LN, true, true, G == 8>(a, smem, tid, [&]() { if (p.qkv) prefetch_w<BNQ>(p.in_w, p.D, tn * BNQ, smem, tid, wave_u); });
+    gemm_phase<BNL, EPI_BIAS_RES_LN, true, true, G == 8>(a, smem, tid, [&]() { if (p.qkv) prefetch_w<BNQ, false, G == 4>(p.in_w, p.D, tn * BNQ, smem, tid, wave_u); });
     if (p.qkv == nullptr) return;      // last layer: the output head follows as its own launch (uniform over the launch)
     group_sync(flags + 16, tn, G, ep, xcc1, p.xln_err, tid);
 
@@ -823,7 +898,7 @@ __global__ __launch_bounds__(256) void encoder_stack_kernel(StackParams p) {
     // adds it as the residual: each workgroup re-reads its OWN columns), but nobody else reads it, so the meeting goes away
     const bool fold = p.w_fold != nullptr;
     gemm_phase<BNL, EPI_EMBED, false, false, G == 8>(a, smem, tid, [&]() {
-        prefetch_w<BNQ, HEAD>(fold ? p.w_fold : p.layer[0].in_w, fold ? p.ldw_fold : p.D, n0q(), smem, tid, wave_u);
+        prefetch_w<BNQ, HEAD, G == 4>(fold ? p.w_fold : p.layer[0].in_w, fold ? p.ldw_fold : p.D, n0q(), smem, tid, wave_u);
     });
     stamp(8, 1);
     a.C = p.qkv; a.ldc = 3 * p.D; a.n0 = n0q();
@@ -861,13 +936,13 @@ __global__ __launch_bounds__(256) void encoder_stack_kernel(StackParams p) {
         a.A = p.ctx; a.lda = p.D; a.W = w.out_w; a.ldw = p.D; a.C = p.y; a.ldc = p.D; a.K = p.D; a.bias = w.out_b;
         a.R = p.h; a.ldr = p.D; a.gamma = w.n1_w; a.beta = w.n1_b; a.n0 = tn * BNL; a.tag28 = (ep + 4u * l) & 0x0fffffffu;
         a.fault = (l == 0) ? (p.fault & 1) : 0;
-        gemm_phase<BNL, EPI_BIAS_RES_LN, false, true, G == 8>(a, smem, tid, [&]() { prefetch_w<BNF>(w.l1_w, p.D, tn * BNF, smem, tid, wave_u); });
+        gemm_phase<BNL, EPI_BIAS_RES_LN, false, true, G == 8>(a, smem, tid, [&]() { prefetch_w<BNF, false, G == 4>(w.l1_w, p.D, tn * BNF, smem, tid, wave_u); });
         stamp(l, 4);
         group_sync(fl + 16, tn, G, ep, xcc1, p.xln_err, tid);
         stamp(l, 5);
 
         a.A = p.y; a.lda = p.D; a.W = w.l1_w; a.ldw = p.D; a.C = p.ff; a.ldc = p.F; a.K = p.D; a.bias = w.l1_b; a.n0 = tn * BNF;
-        gemm_phase<BNF, EPI_BIAS_GELU, true, true, G == 8>(a, smem, tid, [&]() { prefetch_w<BNL>(w.l2_w, p.F, tn * BNL, smem, tid, wave_u); });
+        gemm_phase<BNF, EPI_BIAS_GELU, true, true, G == 8>(a, smem, tid, [&]() { prefetch_w<BNL, false, G == 4>(w.l2_w, p.F, tn * BNL, smem, tid, wave_u); });
         stamp(l, 6);
         group_sync(fl + 24, tn, G, ep, xcc1, p.xln_err, tid);
         stamp(l, 7);
@@ -876,7 +951,7 @@ __global__ __launch_bounds__(256) void encoder_stack_kernel(StackParams p) {
         a.A = p.ff; a.lda = p.F; a.W = w.l2_w; a.ldw = p.F; a.C = p.h; a.ldc = p.D; a.K = p.F; a.bias = w.l2_b;
         a.R = p.y; a.ldr = p.D; a.gamma = w.n2_w; a.beta = w.n2_b; a.n0 = tn * BNL; a.tag28 = (ep + 4u * l + 1u) & 0x0fffffffu;
         a.fault = (l == 0) ? ((p.fault >> 1) & 1) : 0;
-        gemm_phase<BNL, EPI_BIAS_RES_LN, true, true, G == 8>(a, smem, tid, [&]() { if (more) prefetch_w<BNQ, HEAD>(p.layer[l + 1].in_w, p.D, n0q(), smem, tid, wave_u); });
+        gemm_phase<BNL, EPI_BIAS_RES_LN, true, true, G == 8>(a, smem, tid, [&]() { if (more) prefetch_w<BNQ, HEAD, G == 4>(p.layer[l + 1].in_w, p.D, n0q(), smem, tid, wave_u); });
         stamp(l, 8);
         if (!more) {
             if (p.tail) {      // sampling loop: head + DDPM update + the next step's pack close the launch (uniform over the launch)
@@ -961,6 +1036,20 @@ bool encoder_chain_pays(int B) {
     if (B <= 64) return true;
     const int wgs = (B + kNumXCD - 1) / kNumXCD * kNumXCD * 4, rounds = (wgs + 255) / 256;
     return 4 * B * 100 >= 93 * rounds * 256;      // B = 120 (two rounds, 94 % full): the stack is 2.4 % faster; B = 112 stays per GEMM
+}
+
+// The staging addresses of gemm_phase at 4 parts per clip are a scalar base plus a 32-bit byte offset.  The offsets themselves start at a
+// tile's first row and stay within a few MB; the bound is put on whole operands all the same, so that no later change of what the base
+// absorbs can overflow one: activations [M, D | F | 3 D | k_pack] (3 D: qkv, and the fold's econdq rows) and the largest weight.
+bool encoder_chain_addressable(long long M, int D, int F, int k_pack) {
+    if (M <= 0 || D <= 0 || F <= 0 || k_pack < 0) return false;
+    const long long limit = 1ll << 31;
+    long long cols = 3ll * D;
+    if (F > cols) cols = F;
+    if (k_pack > cols) cols = k_pack;
+    const long long wrows = 3ll * D > F ? 3ll * D : F;      // in_proj [3 D, D], linear1 [F, D], linear2 [D, F], w_fold [3 D, k_pack]
+    const long long wcols = D > k_pack ? (D > F ? D : F) : (k_pack > F ? k_pack : F);
+    return M <= limit / 4 / cols && 4 * M * cols < limit && wrows <= limit / 4 / wcols && 4 * wrows * wcols < limit;
 }
 
 // [row tile][layer <= 8, + 1 for the leading embed / QKV phases][meeting point <= 5][part <= 8] (the per-layer chain uses the first 3 x 8

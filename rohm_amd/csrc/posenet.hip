@@ -395,8 +395,9 @@ static EncoderPlan plan_encoder(const rohm_posenet* p, int B, int S) {
     // persistent workgroups fit the batch (encoder_chain_pays: 32, 48 .. 64, 122 .. 128, ...): elsewhere the launch-per-GEMM path
     // picks a tile width per GEMM and keeps more CUs busy (ROHM_POSENET_CHAIN_ANY=1 chains every shape that has the form: tests).
     // Tags: 4 l, 4 l + 1 (the chain's two LayerNorm exchanges and its flags); the head: 60.
+    // Its phases address operands with 32-bit offsets (encoder_chain_addressable: beyond 2^31 bytes per operand, one launch per GEMM).
     e.chained = e.lnf && p->chain && encoder_chain_parts(M, D, p->F) != 0 && 4 * p->L + 2 <= 60 &&
-                ((B >= 32 && encoder_chain_pays(B)) || p->chain_any);
+                ((B >= 32 && encoder_chain_pays(B)) || p->chain_any) && encoder_chain_addressable((long long)B * S, D, p->F, p->KP);
     e.stacked = e.chained && p->chain == 2 && p->H == 4 && p->L <= 8 && S == 144 && D / p->H == 128;
     // The tail phase of a clip reads only what the workgroups of that clip wrote in the same launch, so it is correct for any number
     // of rounds of workgroups (B = 128 runs two: tests/test_gpu_chain.py); the launch never writes the pass counter (common.h
@@ -952,6 +953,10 @@ int rohm_posenet_set_exchange(rohm_posenet_t* h, int on) {
         h->ln_fused = h->head_sk = false;
     }
     return ROHM_OK;
+}
+
+int rohm_posenet_stack_addressable(long long M, int d_model, int d_ff, int k_pack) {
+    return encoder_chain_addressable(M, d_model, d_ff, k_pack) ? 1 : 0;
 }
 
 size_t rohm_posenet_stack_timeline_bytes(int B) {
